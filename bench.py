@@ -2,6 +2,14 @@
 """Batched lockstep Astro physics throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up,
+warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the line.  --full adds every secondary
+measurement (the launches' GPU time, the counters and rooflines, the kernel
+calibration, the rollout, observation and single-game lines, the CPU
+baseline), each in runs of its own after the timed region.
 
 One process per GPU: under torchrun (WORLD_SIZE set) this process is one
 rank; with --gpus N > 1 and no launcher it starts the N ranks itself (one
@@ -68,6 +76,81 @@ def controls(offset, n, nships, ticks, seed=0):
             z = z ^ (z >> np.uint64(31))
             out[t] = ((z >> np.uint64(32)) * np.uint64(6) >> np.uint64(32)).astype(np.int8)
     return out
+
+
+def _i64(c):
+    """A 64-bit constant as the int64 with the same bits."""
+    c %= 1 << 64
+    return c - (1 << 64) if c >= 1 << 63 else c
+
+
+def _lsr(z, k):
+    """Logical right shift of an int64 tensor (torch's >> is arithmetic)."""
+    return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def controls_on(device, offset, n, nships, ticks, seed=0, chunk=64):
+    """`controls` computed on `device` (the same values, bit for bit: int64
+    arithmetic wraps as uint64's does), `chunk` ticks at a time: the set-up
+    cost of a run does not grow with the host's numpy time per tick."""
+    out = torch.empty((ticks, n, nships), dtype=torch.int8, device=device)
+    ids = (torch.arange(offset, offset + n, dtype=torch.int64, device=device)[:, None] * nships
+           + torch.arange(nships, dtype=torch.int64, device=device)[None, :])
+    base = ids * _i64(0x9E3779B97F4A7C15) + _i64(seed)
+    for t0 in range(0, ticks, chunk):
+        t1 = min(ticks, t0 + chunk)
+        add = torch.tensor([_i64((t + 1) * 0xD1B54A32D192ED03) for t in range(t0, t1)],
+                           dtype=torch.int64, device=device)
+        z = base[None] + add[:, None, None]
+        z = (z ^ _lsr(z, 30)) * _i64(0xBF58476D1CE4E5B9)
+        z = (z ^ _lsr(z, 27)) * _i64(0x94D049BB133111EB)
+        z = z ^ _lsr(z, 31)
+        out[t0:t1] = ((_lsr(z, 32) * 6) >> 32).to(torch.int8)
+    return out
+
+
+DUMP_STATE_BYTES = 48 << 20   # the sampled state arrays of --dump-outputs (64 MB in all with the rest)
+
+
+def snapshot_outputs(env, reward, done, seed=0):
+    """What a caller of the timed path holds after its last step, as host
+    arrays for --dump-outputs: reward [N, S] and done [N] of every env, and
+    the state (env-major, as BatchedEnv.obs()) of a fixed sample of envs --
+    all of them while they fit DUMP_STATE_BYTES, else a seeded draw without
+    replacement, sorted (env_index).  Planet and bullet slots past an env's
+    live count hold no game value and are written as 0.  float32, or float64
+    for float64 state and for the integers float32 cannot hold."""
+    torch.cuda.synchronize(env.device)
+    n, S = env.n_env, env.S
+    e = 8 if env.dtype == torch.float64 else 4
+    per_env = e * (5 * S + 4 * env.p_pad + 4 * env.b_cap) + 4 * 4 + 8 + 8
+    m = min(n, DUMP_STATE_BYTES // per_env)
+    idx = np.arange(n) if m == n else np.sort(np.random.RandomState(seed).choice(n, m, replace=False))
+    it = torch.from_numpy(idx).to(env.device)
+    host = lambda t: t.cpu().numpy()  # noqa: E731
+    f = np.float64 if e == 8 else np.float32
+    nplanets, nbullets = host(env.nplanets[it]), host(env.nbullets[it])
+    planets = host(env.planets[:, it].permute(1, 0, 2)).astype(f)
+    bullets = host(env.bullets[it]).astype(f)
+    planets[np.arange(env.p_pad)[None, :] >= nplanets[:, None]] = 0
+    bullets[np.arange(env.b_cap)[None, :] >= nbullets[:, None]] = 0
+    return dict(
+        reward=host(reward).astype(np.float32), done=host(done).astype(np.float32),
+        env_index=(idx + env.env_offset).astype(np.float64),
+        ships=host(env.ships[:, it].permute(1, 0, 2)).astype(f),
+        ships_b=host(env.ships_b[:, it].permute(1, 0)).astype(f), planets=planets, bullets=bullets,
+        tick=host(env.tick[it]).astype(np.float32), nplanets=nplanets.astype(np.float32),
+        nbullets=nbullets.astype(np.float32), flags=host(env.flags[it]).astype(np.float32),
+        game_seed=host(env.game_seed[it]).view(np.uint32).astype(np.float64))
+
+
+def write_outputs(path, arrays, rank, world):
+    """DIR/<name>.npy, one file per array (DIR/<name>.rank<r>.npy for the
+    ranks of a multi-GPU run: each holds its own shard)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + ('.rank%d' % rank if world > 1 else '') + '.npy'), a)
 
 
 def _cpu_worker(args):
@@ -317,13 +400,14 @@ def stub_rank(args, world, rank):
                    higher_is_better=True, scaling='weak', vs_baseline=None, stub=True,
                    roofline=dict(bound='hbm', achieved=0.0, peak=HBM_PEAK_GBS, unit='GB/s', frac=0.0, traffic=None,
                                  scope='stub', aggregate=aggregate_roofline(bytes_all, args.steps, wall, n_ranks)))
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             add_cpu_baseline(out, WORKLOADS[args.workload], args)
         print(json.dumps(out), flush=True)
 
 
 PROFILE_ROUNDS = ('round6', 'round5', 'round4', 'round3', 'round2')
 ROLLOUT_LAUNCHES = 10   # the rollout line's launches at least
+WARM_NOMINAL_STEP_US = 10.0   # one c3 launch on the GPU (profiles/round6: 9.6 us): sizes the --warm-ms rounds
 
 
 def profile_file(name):
@@ -341,6 +425,13 @@ def main():
     ap.add_argument('--steps', type=int, default=1000)
     ap.add_argument('--warmup', type=int, default=50)
     ap.add_argument('--workload', default='c3', choices=sorted(WORKLOADS))
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run every secondary measurement: the launches\' GPU time, '
+                         'the counters and rooflines, the kernel calibration, the rollout, observation and '
+                         'single-game lines and the CPU baseline (a plain run prints the headline fields only)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step computed (reward, done, and the state of a fixed sample '
+                         'of envs) as DIR/<name>.npy, float32 or float64, at most 64 MB in all')
     ap.add_argument('--counters-in-region', action='store_true',
                     help='time the launches that count (stats rows) instead of counting in K further launches')
     ap.add_argument('--n-env', type=int, default=0, help='override envs per GPU')
@@ -417,6 +508,7 @@ def main():
         else:
             dist.init_process_group(backend)
 
+    full = args.full
     wl = WORKLOADS[args.workload]
     cfg = DEFAULT_CONFIG._replace(**wl['cfg'])
     n = args.n_env or wl['n']
@@ -428,7 +520,7 @@ def main():
     if args.burn_in > 0:   # age the batch: games of every age, bullets in flight
         env.rollout(args.burn_in, 'random', tick0=1 << 40, stats=False)
     ticks = args.warmup + args.steps
-    ctl = torch.from_numpy(controls(offset, n, env.S, ticks)).to(dev)
+    ctl = controls_on(dev, offset, n, env.S, ticks)
     ptrs = [ctl[t].data_ptr() for t in range(ticks)]
     stream = torch.cuda.current_stream(dev)
 
@@ -465,6 +557,7 @@ def main():
     # before the region: its first replay uploads it.
     head = min(args.steps, max(0, args.eager_head)) if args.graph > 0 else args.steps
     graphs, replays, graph_sizes = [], [], []
+    warm_rounds = 0
     use_c = args.launcher == 'c'
     if use_c:   # the K launches issued from C (astro_step_many), per-tick outputs
         head = 0
@@ -512,7 +605,7 @@ def main():
             replays = [raw(g.raw_cuda_graph_exec()) for g in graphs]
         for r in replays:   # (the first replay uploads the graph)
             r()
-        if not cnt:
+        if full and not cnt:
             # the statistics at the region's start, read BEFORE the warm
             # replays: the launches they and the region run leave the stats
             # rows alone, and the region then follows the warm replays with
@@ -524,12 +617,17 @@ def main():
         # games with the same graphs: on a box that idled before this process
         # the first short region ran at 20 us per step on the GPU's own
         # timeline, the next ones at 13 (profiles/round3s2/bench_c3_20_reps.jsonl).
-        # Bounded on the GPU's progress, not the host's: each round of replays
-        # is waited for before the next is queued, so at most one round is
-        # in flight when the time is up
-        t_w = time.perf_counter()
+        # Each round of replays is waited for before the next is queued, so
+        # at most one round is in flight.  The rounds are counted, not
+        # clocked: --warm-ms over the round's nominal GPU time (the replayed
+        # launches at WARM_NOMINAL_STEP_US each), so the region starts from
+        # the same games in every run of the same arguments and
+        # --dump-outputs of two runs can be compared
         ev_w = torch.cuda.Event()
-        while time.perf_counter() - t_w < args.warm_ms * 1e-3:
+        warm_rounds = 0
+        if args.warm_ms > 0:
+            warm_rounds = max(1, int(np.ceil(args.warm_ms * 1e3 / (WARM_NOMINAL_STEP_US * (args.steps - head)))))
+        for _ in range(warm_rounds):
             for r in replays:
                 r()
             ev_w.record(stream)
@@ -537,7 +635,8 @@ def main():
                 pass
     if cnt or not graphs:
         barrier()
-        s0 = env.stat_dict()
+        if full:
+            s0 = env.stat_dict()
     barrier()
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     poll_event = args.end_poll == 'event'
@@ -573,6 +672,59 @@ def main():
     # faults of the timed region (read before stat_dict, which raises on them)
     dev_err = env.device_errors(clear=False)
     barrier()
+    if args.dump_outputs:   # (before any further launch: the last timed step's reward, done and state)
+        write_outputs(args.dump_outputs, snapshot_outputs(env, rew_k[-1] if use_c else env.reward,
+                                                          done_k[-1] if use_c else env.done), rank, world)
+
+    def headline(wall_max, n_dev, errors):
+        """The fields every line has: the headline figure of the timed
+        region and what it ran."""
+        return dict(
+            metric=METRIC, value=n * world * args.steps / wall_max, unit='env-steps/s', n_gpus=n_dev, ranks=world,
+            steps=args.steps, warmup=args.warmup, ms_per_step=wall_max / args.steps * 1e3, higher_is_better=True,
+            scaling='weak', vs_baseline=None,
+            dtype='f64' if args.state == 'f64' else 'f64 math / f32 state',
+            data='synthetic (random actions; games from generate_configs seed streams)',
+            config=dict(workload='%s: %s' % (args.workload, wl['desc']), n_env_per_gpu=n,
+                        n_env_total=n * world, b_cap=wl['b_cap'], p_pad=wl['p_pad'],
+                        state=args.state, parallelism='env-shard x%d (no collectives)' % world),
+            timed_region=('%d launches issued from C in one astro_step_many call' % args.steps) if use_c else
+                         '%d launches: %d eager, then %s' % (
+                args.steps, head, ('%d hipGraph replay(s) of %s launches (%s), each graph replayed once '
+                                   'untimed before the region' % (
+                                       len(graphs), '+'.join(str(x) for x in graph_sizes) if len(graphs) <= 16 else
+                                       '%d..%d' % (min(graph_sizes), max(graph_sizes)),
+                                       'hipGraphLaunch' if args.replay == 'raw' else 'torch CUDAGraph.replay'))
+                if graphs else 'no graph'),
+            dist=dict(initialized=dist_on, backend=backend if dist_on else None, world=world,
+                      barrier=('host-side gloo group' if bar_group is not None else
+                               (backend if dist_on else None)),
+                      reductions='device tensors (RCCL all_reduce)' if dist_on and red_dev is not None
+                      else ('host tensors (gloo)' if dist_on else 'none (one rank)')),
+            burn_in_ticks=args.burn_in, settle_launches=settle, warm_ms=args.warm_ms, warm_rounds=warm_rounds,
+            full=full, device_errors=int(errors))
+
+    def finish(out, errors):
+        """Leave the process group; rank 0 prints the line (after its
+        host-side CPU baseline under --full) and fails on device error bits."""
+        if dist_on:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        if rank == 0:
+            if full and not args.no_cpu:
+                add_cpu_baseline(out, wl, args)
+            print(json.dumps(out), flush=True)
+            if int(errors):
+                raise SystemExit('bench: a launch reported device error bits (device_errors=%d): the state '
+                                 'and the line above are not trusted' % int(errors))
+
+    if not full:
+        # a plain run ends here: the reductions of the timed region alone
+        wall_max = _shard.max_over_ranks(wall, device=red_dev)
+        err_all, n_dev = _shard.sum_over_ranks([dev_err, 1 if local < torch.cuda.device_count() else 0],
+                                               device=red_dev)
+        return finish(headline(wall_max, int(n_dev), err_all) if rank == 0 else None, err_all)
+
     s1 = env.stat_dict() if not dev_err else dict(s0)
     gpu_ms_stream = ev0.elapsed_time(ev1) / args.steps if poll_event else None
     gpu_ms_graph = None
@@ -703,9 +855,9 @@ def main():
     # every rank's section 8(d) bytes per launch, summed: the aggregate roofline
     bytes_all = float(_shard.sum_over_ranks([bytes_launch], device=red_dev)[0])
 
+    out = None
     if rank == 0:
         n_total = n * world
-        value = n_total * args.steps / wall_max
         # per-launch duration = the K launches' GPU time / K (event-record
         # nodes inside the graphs: kernels plus the gaps between them, not the
         # host's submission); rocprofv3's kernel average is compared with it
@@ -764,14 +916,7 @@ def main():
                              waves_counted=pj['waves'], step_waves=sw, helper_waves=hw,
                              valu_per_wave_both_roles=pj['valu_per_wave'], source=pj.get('_path'), note=note)
         out = dict(
-            metric=METRIC, value=value, unit='env-steps/s', n_gpus=n_dev, ranks=world, steps=args.steps,
-            warmup=args.warmup, ms_per_step=wall_max / args.steps * 1e3, higher_is_better=True,
-            scaling='weak', vs_baseline=None,
-            dtype='f64' if args.state == 'f64' else 'f64 math / f32 state',
-            data='synthetic (random actions; games from generate_configs seed streams)',
-            config=dict(workload='%s: %s' % (args.workload, wl['desc']), n_env_per_gpu=n,
-                        n_env_total=n_total, b_cap=wl['b_cap'], p_pad=wl['p_pad'],
-                        state=args.state, parallelism='env-shard x%d (no collectives)' % world),
+            headline(wall_max, n_dev, tot[7]),
             roofline=dict(bound='hbm', achieved=achieved, peak=HBM_PEAK_GBS, unit='GB/s',
                           frac=achieved / HBM_PEAK_GBS, traffic=traffic,
                           scope=('per GPU: rank 0\'s dominant kernel on its own GPU' if world > 1
@@ -791,20 +936,6 @@ def main():
                       '%d further launches right after the timed region, continuing its games, of the instance that '
                       'counts (stats rows; the timed region runs the one without counters, as a caller passing no '
                       'stats buffer does): the stats below and the section 8(d) bytes per launch' % args.steps),
-            timed_region=('%d launches issued from C in one astro_step_many call' % args.steps) if use_c else
-                         '%d launches: %d eager, then %s' % (
-                args.steps, head, ('%d hipGraph replay(s) of %s launches (%s), each graph replayed once '
-                                   'untimed before the region' % (
-                                       len(graphs), '+'.join(str(x) for x in graph_sizes),
-                                       'hipGraphLaunch' if args.replay == 'raw' else 'torch CUDAGraph.replay'))
-                if graphs else 'no graph'),
-            dist=dict(initialized=dist_on, backend=backend if dist_on else None, world=world,
-                      barrier=('host-side gloo group' if bar_group is not None else
-                               (backend if dist_on else None)),
-                      reductions='device tensors (RCCL all_reduce)' if dist_on and red_dev is not None
-                      else ('host tensors (gloo)' if dist_on else 'none (one rank)')),
-            burn_in_ticks=args.burn_in, settle_launches=settle, warm_ms=args.warm_ms,
-            device_errors=int(tot[7]),
             stats=dict(mean_live_bullets=mlb,
                        serial_resets_per_step=d.get('serial_resets', 0) / args.steps,
                        resets_per_step=rps, overflow_bullets=tot[2],
@@ -818,16 +949,7 @@ def main():
     # rank 0's host-side lines run after every rank has left the GPU region
     # (the last collective above): the CPU baseline of the same workload, on
     # this rank's CPU share, for any number of ranks
-    if dist_on:
-        import torch.distributed as dist
-        dist.destroy_process_group()
-    if rank == 0:
-        if not args.no_cpu:
-            add_cpu_baseline(out, wl, args)
-        print(json.dumps(out), flush=True)
-        if int(tot[7]):
-            raise SystemExit('bench: a launch reported device error bits (device_errors=%d): the state '
-                             'and the line above are not trusted' % int(tot[7]))
+    finish(out, tot[7])
 
 
 if __name__ == '__main__':

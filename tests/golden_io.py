@@ -2,6 +2,7 @@
 
 The fixtures were written by tools/gen_golden.py from the reference itself;
 this module only reads data (npz with allow_pickle=False, json)."""
+import io
 import json
 import os
 
@@ -20,7 +21,21 @@ def configs():
 
 
 def load(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """np.load of a fixture.  A fixture too large for one committed file is
+    stored as consecutive byte ranges name.00, name.01, ... (tools/
+    gen_golden.py: split_large) and read back as one."""
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    parts = sorted(f for f in os.listdir(GOLDEN)
+                   if f.startswith(name + '.') and f[len(name) + 1:].isdigit())
+    if not parts:
+        raise FileNotFoundError(path)
+    data = b''
+    for f in parts:
+        with open(os.path.join(GOLDEN, f), 'rb') as fh:
+            data += fh.read()
+    return np.load(io.BytesIO(data), allow_pickle=False)
 
 
 def load_json(name):

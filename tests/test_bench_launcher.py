@@ -39,7 +39,7 @@ def test_multi_rank_line_carries_roofline_and_cpu_baseline():
     2-rank line carries the per-GPU roofline with an aggregate over ranks and
     the CPU baseline (rank 0, after every rank left the GPU region), through
     the same code path as a real rank."""
-    p, lines = _run(['--gpus', '2', '--steps', '5', '--stub', '--cpu-seconds', '0.3', '--cpu-procs', '1'])
+    p, lines = _run(['--gpus', '2', '--steps', '5', '--stub', '--full', '--cpu-seconds', '0.3', '--cpu-procs', '1'])
     assert p.returncode == 0, p.stderr
     j = json.loads(lines[0])
     assert {'roofline', 'cpu_baseline'} <= set(j)
@@ -48,6 +48,31 @@ def test_multi_rank_line_carries_roofline_and_cpu_baseline():
     assert abs(agg['achieved'] - 2 * 1000 * 5 / 0.002 / 1e9) < 1e-12
     cb = j['cpu_baseline']
     assert cb['cores'] == 1 and cb['kind'] == 'port' and cb['value'] > 0
+
+
+def test_plain_line_runs_no_cpu_baseline():
+    """Without --full the line has the headline fields and nothing that takes
+    a run of its own: no CPU baseline, although --no-cpu is not given."""
+    p, lines = _run(['--gpus', '1', '--steps', '5', '--warmup', '2', '--stub'])
+    assert p.returncode == 0, p.stderr
+    j = json.loads(lines[0])
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'ms_per_step'} <= set(j)
+    assert j['steps'] == 5 and j['warmup'] == 2
+    assert 'cpu_baseline' not in j and 'speedup_vs_cpu' not in j
+
+
+def test_device_controls_equal_the_host_controls():
+    """bench.controls_on (torch int64 arithmetic, what a run fills its control
+    buffers with) == bench.controls (numpy uint64), bit for bit: several
+    chunks of ticks, a ragged last chunk, a shard offset, ids past 2^32."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    for off, n, s, ticks, seed in [(0, 257, 2, 130, 0), (7 * 65536 + 3, 100, 2, 65, 5), (1 << 33, 64, 3, 3, 0)]:
+        want = bench.controls(off, n, s, ticks, seed)
+        got = bench.controls_on('cpu', off, n, s, ticks, seed).numpy()
+        assert got.dtype == np.int8 and np.array_equal(got, want)
+        assert want.min() == 0 and want.max() == 5
 
 
 def test_four_ranks_and_single_rank():

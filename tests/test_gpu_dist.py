@@ -33,7 +33,7 @@ def test_bench_rank_over_rccl_at_world_size_one():
     env = dict(os.environ, ASTRO_DIST_INIT='1', ASTRO_DIST_BACKEND='nccl', RANK='0', LOCAL_RANK='0',
                WORLD_SIZE='1', LOCAL_WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()),
                PYTHONDONTWRITEBYTECODE='1')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '6', '--warmup', '2',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '6', '--warmup', '2', '--full',
            '--burn-in', '20', '--rollout', '4', '--no-features', '--no-single', '--calib', '4',
            '--cpu-seconds', '0.5', '--cpu-procs', '1', '--n-env', '4096', '--warm-ms', '2']
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)

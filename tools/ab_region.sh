@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out/ab_region.jsonl
 for k in $(seq 1 ${N:-4}); do
   for v in ${VARS:-A B}; do
-    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu --no-single --no-features --rollout 0 ${!v} \
+    timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-single --no-features --rollout 0 ${!v} \
       > /tmp/abr.json 2> /tmp/abr.err
     rc=$?
     if [ $rc -ne 0 ]; then tail -5 /tmp/abr.err; exit $rc; fi

@@ -16,6 +16,7 @@ are committed.  Nothing here is imported by the product package.
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py
 """
+import io
 import itertools as it
 import json
 import os
@@ -478,7 +479,7 @@ def _import_rl():
 
 def gen_features():
     rl = _import_rl()
-    z = np.load(os.path.join(OUT, 'steps.npz'))
+    z = load_fixture('steps.npz')
     names = list(z['cfg_names'])
     feats, rows, dims = [], [], []
     for i in range(z['tick'].shape[0]):
@@ -545,7 +546,7 @@ def gen_log():
 #    for each ship's ego view (core.roll_ships, core.py:306-327)
 
 def gen_script_controls():
-    z = np.load(os.path.join(OUT, 'steps.npz'))
+    z = load_fixture('steps.npz')
     names = list(z['cfg_names'])
     out = np.full((z['tick'].shape[0], S_PAD), -1, dtype=np.int8)
     bots = {}
@@ -663,7 +664,7 @@ def gen_long_games():
     print('wrote long_games.npz', [(r['key'], r['ticks'], r['winner']) for r in index])
 
 
-def main():
+def generate():
     if sys.argv[1:] == ['config1']:
         gen_config1()
         return
@@ -694,6 +695,47 @@ def main():
     gen_script_controls()
     gen_config1()
     gen_long_games()
+
+
+# No committed file may exceed 1 MiB: a larger fixture is stored as consecutive
+# byte ranges name.00, name.01, ... (tests/golden_io.py: load joins them).
+PART_BYTES = 1000000
+
+
+def fixture_parts(name):
+    return sorted(os.path.join(OUT, f) for f in os.listdir(OUT)
+                  if f.startswith(name + '.') and f[len(name) + 1:].isdigit())
+
+
+def load_fixture(name):
+    path = os.path.join(OUT, name)
+    if os.path.exists(path):
+        return np.load(path)
+    data = b''
+    for f in fixture_parts(name):
+        with open(f, 'rb') as fh:
+            data += fh.read()
+    return np.load(io.BytesIO(data))
+
+
+def split_large():
+    for name in sorted(os.listdir(OUT)):
+        path = os.path.join(OUT, name)
+        if name.endswith('.npz') and os.path.getsize(path) > PART_BYTES:
+            for f in fixture_parts(name):
+                os.remove(f)
+            with open(path, 'rb') as fh:
+                data = fh.read()
+            for k in range(0, len(data), PART_BYTES):
+                with open('%s.%02d' % (path, k // PART_BYTES), 'wb') as fh:
+                    fh.write(data[k:k + PART_BYTES])
+            os.remove(path)
+            print('split', name, 'into', -(-len(data) // PART_BYTES), 'parts')
+
+
+def main():
+    generate()
+    split_large()
 
 
 if __name__ == '__main__':

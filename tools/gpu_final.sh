@@ -10,7 +10,7 @@ O=gpurun_out/final
 mkdir -p $O
 b() {   # name limit args...
   local name=$1 limit=$2; shift 2
-  timeout -k 10 "$limit" python bench.py "$@" > $O/$name.json 2> $O/$name.err
+  timeout -k 10 "$limit" python bench.py --full "$@" > $O/$name.json 2> $O/$name.err
   local rc=$?
   echo "$name rc=$rc"; cat $O/$name.json | cut -c1-400
   if [ $rc -ne 0 ]; then tail -5 $O/$name.err; exit $rc; fi

@@ -29,7 +29,7 @@ fi
 if [ -n "${BENCH_VARS:-}" ]; then
   while IFS= read -r args; do
     [ -z "$args" ] && continue
-    timeout -k 10 300 python bench.py $args > $O/bench_one.json 2> $O/bench.err
+    timeout -k 10 300 python bench.py --full $args > $O/bench_one.json 2> $O/bench.err
     rc=$?
     if [ $rc -ne 0 ]; then echo "bench rc=$rc: $args"; tail -5 $O/bench.err; exit $rc; fi
     python - "$args" <<'PY' >> $O/bench.jsonl

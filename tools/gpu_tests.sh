@@ -20,6 +20,6 @@ if [ "${FULL:-0}" = 1 ]; then
   step full 1100 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  step bench 600 python bench.py ${BENCH_ARGS:-}
+  step bench 600 python bench.py --full ${BENCH_ARGS:-}
 fi
 exit 0

@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/pmc
-ARGS="${PMC_BENCH_ARGS:---steps 200 --warmup 20 --no-cpu}"
+ARGS="${PMC_BENCH_ARGS:---full --steps 200 --warmup 20 --no-cpu}"
 i=0
 for ctrs in "$@"; do
   i=$((i+1))

@@ -15,7 +15,7 @@ for lib in ${LIBS:-libastro_hip}; do
               "SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_FMA_F64 SQ_ACTIVE_INST_LDS"; do
     i=$((i+1))
     ASTRO_LIB=$PWD/astro_amd/$lib.so timeout -k 10 300 rocprofv3 --kernel-trace --pmc $ctrs -d $OUT/${lib}_$i -o run -f csv -- \
-        python bench.py --workload $WL --steps 200 --warmup 20 --no-cpu --no-single --no-features --rollout 0 --graph 0 --calib 10 \
+        python bench.py --full --workload $WL --steps 200 --warmup 20 --no-cpu --no-single --no-features --rollout 0 --graph 0 --calib 10 \
         > $OUT/${lib}_$i.log 2>&1
     rc=$?; echo "$lib pass $i rc=$rc"
     if [ $rc -ne 0 ]; then tail -5 $OUT/${lib}_$i.log; exit $rc; fi

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 WL=${WL:-c3}
 OUT=gpurun_out/r2prof/$WL
 mkdir -p $OUT
-ARGS="--workload $WL --no-cpu ${EXTRA_ARGS:-}"
+ARGS="--full --workload $WL --no-cpu ${EXTRA_ARGS:-}"
 run() {
   local tag=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace "$@" -d $OUT/$tag -o run -f csv -- python bench.py $ARGS > $OUT/$tag.log 2>&1

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 WL=${WL:-c3}
 OUT=${OUT:-gpurun_out/prof/$WL}
 mkdir -p $OUT
-ARGS="--workload $WL --no-cpu --no-single --no-features --steps ${PSTEPS:-300} ${EXTRA_ARGS:-}"
+ARGS="--full --workload $WL --no-cpu --no-single --no-features --steps ${PSTEPS:-300} ${EXTRA_ARGS:-}"
 run() {
   local tag=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace "$@" -d $OUT/$tag -o run -f csv -- python bench.py $ARGS > $OUT/$tag.log 2>&1
