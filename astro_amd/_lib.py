@@ -1,4 +1,5 @@
-"""ctypes binding of libastro_hip.so (include/astro_step.h).
+"""ctypes binding of libastro_hip.so (include/astro_step.h) and of
+libastro_qnet.so (include/astro_qnet.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -156,7 +157,31 @@ _SYMBOLS = {
                                      ctypes.c_void_p]),
 }
 
+
+
+class AstroQNet(ctypes.Structure):
+    """include/astro_qnet.h AstroQNet: the packed Q-network of astro_qvalues."""
+    _fields_ = [
+        ('weights', ctypes.c_void_p),
+        ('nships', ctypes.c_int32),
+        ('nout', ctypes.c_int32),
+    ]
+
+
+# libastro_qnet.so: a library of its own (libastro_hip.so and _SYMBOLS stay what they are)
+QNET_LIB_PATH = os.environ.get('ASTRO_QNET_LIB') or os.path.join(HERE, 'libastro_qnet.so')
+QNET_ABI_VERSION = 1
+QNET_HIDDEN = 32
+_QNET_SYMBOLS = {
+    'astro_qnet_abi_version': (ctypes.c_int, []),
+    'astro_qnet_last_error': (ctypes.c_char_p, []),
+    'astro_qvalues': (ctypes.c_int, [ctypes.POINTER(AstroParams), ctypes.POINTER(AstroState),
+                                     ctypes.POINTER(AstroQNet), ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.POINTER(AstroPolicy), ctypes.c_double, ctypes.c_void_p]),
+}
+
 _lib = None
+_qnet_lib = None
 
 
 class AstroError(RuntimeError):
@@ -193,4 +218,31 @@ def load(path=LIB_PATH):
 def check(rc, what):
     if rc != 0:
         msg = load().astro_last_error().decode(errors='replace')
+        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
+
+
+def load_qnet(path=QNET_LIB_PATH):
+    """Load (once) and type libastro_qnet.so.  Raises if it is absent or stale."""
+    global _qnet_lib
+    if _qnet_lib is not None:
+        return _qnet_lib
+    if not os.path.exists(path):
+        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
+                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in _QNET_SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.astro_qnet_abi_version()
+    if v != QNET_ABI_VERSION:
+        raise AstroError('libastro_qnet.so ABI %d != expected %d (rebuild)' % (v, QNET_ABI_VERSION))
+    _qnet_lib = lib
+    return lib
+
+
+def check_qnet(rc, what):
+    if rc != 0:
+        msg = load_qnet().astro_qnet_last_error().decode(errors='replace')
         raise AstroError('%s failed (%d): %s' % (what, rc, msg))

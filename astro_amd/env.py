@@ -489,6 +489,76 @@ class BatchedEnv:
                                            out.data_ptr(), rows, _stream_ptr(self.device)), 'astro_features')
         return out
 
+    # ------------------------------------------------------- Q-network policy
+
+    def _qvalues(self, net, q, control, explore, epsilon):
+        if net.weights.device != self.hdr.device:
+            raise ValueError('the network is on %s, the env on %s' % (net.weights.device, self.hdr.device))
+        qlib = _lib.load_qnet()
+        _lib.check_qnet(qlib.astro_qvalues(
+            ctypes.byref(self.params), ctypes.byref(self.state), net.byref(),
+            None if q is None else q.data_ptr(), None if control is None else control.data_ptr(),
+            None if explore is None else ctypes.byref(explore), float(epsilon),
+            _stream_ptr(self.device)), 'astro_qvalues')
+
+    def _q_buffer(self, net, out):
+        shape = (self.n_env, self.S, net.nout)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
+                or not out.is_contiguous()):
+            raise ValueError('out must be a contiguous float32 %s tensor on %s' % (list(shape), self.device))
+        return out
+
+    def qvalues(self, net, out=None):
+        """rl.ValueNetwork.forward (rl.py:137-155) of every ship's ego view of
+        every env's current state: float32 [N, S, nout], computed by one
+        kernel straight from the state arrays (astro_qvalues; ``net`` is an
+        astro_amd.qnet.QNetwork).  The values are those of the network on
+        ``features()`` and its column-swapped copy, to float32 rounding."""
+        q = self._q_buffer(net, out)
+        self._qvalues(net, q, None, None, 0.0)
+        return q
+
+    def qcontrols(self, net, epsilon=0.0, seed=0, tick0=0, q_out=None):
+        """rl.QBot's decision for every ship (rl.py:195-209): int8 [N, S], the
+        first maximal index of ``qvalues(net)`` -- or, with probability
+        ``epsilon`` per ship and tick, the control ``controls('random', seed,
+        tick0)`` draws (keyed by global ship id, so shards agree; epsilon = 1
+        is exactly that policy).  q_out: a float32 [N, S, nout] tensor that
+        also receives the Q values."""
+        q = None if q_out is None else self._q_buffer(net, q_out)
+        control = torch.empty((self.n_env, self.S), dtype=torch.int8, device=self.device)
+        explore = None
+        if epsilon != 0.0:
+            explore = _lib.AstroPolicy(kind=_lib.POLICIES['random'], seed=int(seed), tick0=int(tick0),
+                                       env_offset=self.env_offset)
+        self._qvalues(net, q, control, explore, epsilon)
+        return control
+
+    def rollout_q(self, net, ticks, epsilon=0.0, seed=0, tick0=0, opponent=None, auto_reset=None):
+        """``ticks`` steps driven by the network: each tick ``qcontrols(net,
+        epsilon, seed, tick0 + t)`` then ``step`` (a host loop of two launches
+        per tick).  opponent: None (the network plays every ship) or
+        'script' / 'nothing' / 'random': ship 1's controls come from
+        ``controls(opponent, seed, tick0 + t)``.  Returns (reward [ticks, N,
+        S], done [ticks, N], control [ticks, N, S])."""
+        ticks = int(ticks)
+        if opponent is not None and (self.S != 2 or opponent not in ('script', 'nothing', 'random')):
+            raise ValueError("opponent needs a two-ship env and one of 'script', 'nothing', 'random'")
+        reward = torch.empty((ticks, self.n_env, self.S), dtype=torch.float32, device=self.device)
+        done = torch.empty((ticks, self.n_env), dtype=torch.uint8, device=self.device)
+        control = torch.empty((ticks, self.n_env, self.S), dtype=torch.int8, device=self.device)
+        for t in range(ticks):
+            c = self.qcontrols(net, epsilon, seed, tick0 + t)
+            if opponent is not None:
+                c[:, 1] = self.controls(opponent, seed, tick0 + t)[:, 1]
+            control[t] = c
+            _, r, d = self.step(control[t], auto_reset=auto_reset)
+            reward[t] = r
+            done[t] = d
+        return reward, done, control
+
     def stat_dict(self):
         v = self.stats.sum(0).cpu().tolist()
         self.check_errors()

@@ -1,0 +1,257 @@
+"""CPU-only checks of the Q-network policy's host side (astro_amd/qnet.py,
+include/astro_qnet.h, tests/golden/qnet.npz)."""
+import ctypes
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+import __graft_entry__
+from astro_amd import _lib, core, qnet
+from astro_amd.config import DEFAULT_CONFIG
+from oracle import port
+from tests import golden_io as gio
+from tests import qnet_util as qu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'astro_qnet.h')
+
+
+def _module(name, dtype=torch.float32):
+    fx, _, _ = qu.fixture()
+    m = qnet.ValueNetwork(name == 'solo', 6).to(dtype)
+    m.load_state_dict({k: torch.as_tensor(v) for k, v in fx[name]['weights'].items()})
+    return m
+
+
+def test_fixture_is_what_the_issue_describes():
+    fx, q32, q64 = qu.fixture()
+    tr = gio.Transitions('steps.npz')
+    assert q32.shape == q64.shape == (tr.n, 2, 6) and q32.dtype == np.float32 and q64.dtype == np.float64
+    solo = tr.z['nships'] == 1
+    assert not q32[solo, 1].any() and not q64[solo, 1].any()
+    for name, rows in (('duo', ~solo), ('solo', solo)):
+        S = 1 if name == 'solo' else 2
+        e = np.abs(q32[rows, :S].astype(np.float64) - q64[rows, :S]).max()
+        assert e == fx[name]['e_ref'] and 1e-7 < e < 2e-6
+        assert fx[name]['weights']['f0.weight'].shape == (32, 5 + 5 * S)
+    # the scaled network is not a constant policy, and no decision is a near tie
+    duo = q64[~solo]
+    assert len(set(np.argmax(duo, -1).flatten().tolist())) >= 3
+    top = np.sort(duo, -1)
+    assert (top[..., -1] - top[..., -2]).min() > 2 * fx['duo']['tol']
+
+
+@pytest.mark.parametrize('name', ['duo', 'solo'])
+def test_pack_unpack_round_trip(name):
+    fx, _, _ = qu.fixture()
+    w = fx[name]['weights']
+    S = 1 if name == 'solo' else 2
+    flat = qnet.pack(w)
+    assert flat.dtype == np.float32 and flat.size == 32 * (5 + 5 * S) + 32 + 4 * (32 * 32 + 32) + 33 * 6
+    assert flat.size == (4934 if S == 2 else 4774)
+    back = qnet.unpack(flat, S, 6)
+    assert list(back) == list(qu.NAMES)
+    for k in qu.NAMES:
+        assert np.array_equal(back[k], w[k]), k
+    # a module packs as its state_dict, in state_dict order
+    m = _module(name)
+    assert list(m.state_dict()) == list(qu.NAMES)
+    assert np.array_equal(qnet.pack(m), flat)
+    assert np.array_equal(flat[:32 * (5 + 5 * S)].reshape(32, -1), w['f0.weight'])
+    assert np.array_equal(flat[-6:], w['v0.bias'])
+    with pytest.raises(ValueError):
+        qnet.unpack(flat[:-1], S, 6)
+
+
+def test_ctypes_struct_layout_matches_header():
+    """sizeof/offsetof of AstroQNet (gcc on include/astro_qnet.h) equal the ctypes mirror's."""
+    st = _lib.AstroQNet
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "astro_qnet.h"', 'int main(void){',
+             'printf("%%zu\\n", sizeof(%s));' % st.__name__]
+    expect = [ctypes.sizeof(st)]
+    for f, _ in st._fields_:
+        lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (st.__name__, f))
+        expect.append(getattr(st, f).offset)
+    lines += ['printf("%d\\n", ASTRO_QNET_ABI_VERSION);', 'printf("%d\\n", ASTRO_QNET_HIDDEN);', 'return 0;}']
+    expect += [_lib.QNET_ABI_VERSION, _lib.QNET_HIDDEN]
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, 'layout.c')
+        exe = os.path.join(d, 'layout')
+        open(src, 'w').write('\n'.join(lines))
+        subprocess.check_call(['gcc', '-std=c99', '-I', os.path.dirname(HEADER), src, '-o', exe])
+        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
+    assert got == expect
+
+
+def test_library_exports_every_header_symbol():
+    __graft_entry__.build()
+    text = open(HEADER).read()
+    names = sorted(set(re.findall(r'^\s*(?:const\s+)?\w+\s*\*?\s*(astro_\w+)\s*\(', text, re.M)))
+    assert set(names) == {'astro_qnet_abi_version', 'astro_qnet_last_error', 'astro_qvalues'} == set(_lib._QNET_SYMBOLS)
+    out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.QNET_LIB_PATH], text=True)
+    exported = set(re.findall(r' T (astro_\w+)$', out, re.M))
+    assert set(names) <= exported
+    lib = _lib.load_qnet()
+    for n in names:
+        getattr(lib, n)
+    assert lib.astro_qnet_abi_version() == _lib.QNET_ABI_VERSION
+
+
+def test_bad_arguments_without_gpu():
+    """astro_qvalues rejects bad arguments before it touches the device."""
+    __graft_entry__.build()
+    lib = _lib.load_qnet()
+    P = _lib.AstroParams(nships=2, solo=0, p_pad=4, max_planets=4, b_cap=32)
+    S = _lib.AstroState(n_env=0)
+    net = _lib.AstroQNet(weights=None, nships=2, nout=6)
+    q = ctypes.c_void_p(16)
+
+    def call(p=P, s=S, n=net, qq=q, c=None, eps=0.0):
+        rc = lib.astro_qvalues(ctypes.byref(p), ctypes.byref(s), ctypes.byref(n), qq, c, None, eps, None)
+        return rc, lib.astro_qnet_last_error().decode()
+    assert call()[0] == 0                       # no envs: nothing to do
+    rc, msg = call(n=_lib.AstroQNet(nships=1, nout=6))
+    assert rc < 0 and 'nships' in msg
+    for nout in (0, 7):
+        rc, msg = call(n=_lib.AstroQNet(nships=2, nout=nout))
+        assert rc < 0 and 'nout' in msg
+    rc, msg = call(qq=None)
+    assert rc < 0 and 'both NULL' in msg
+    for eps in (-0.5, 1.0001, float('nan')):
+        rc, msg = call(eps=eps)
+        assert rc < 0 and 'epsilon' in msg
+
+
+def _golden_features(tr, feats, i):
+    """[(ship, features of its ego view)] of golden state i (ego 1 by the column swap)."""
+    f = feats.of(i)
+    return [(0, f)] if int(tr.z['nships'][i]) == 1 else [(0, f), (1, qnet.swap_ego(f))]
+
+
+def test_value_network_reproduces_q32_and_forward64_q64():
+    """The project's torch ValueNetwork, loaded with the fixture weights, gives
+    the reference's float32 Q values within tol on the golden features; the
+    numpy float64 forward gives the fixture's q64 to 1e-12."""
+    fx, q32, q64 = qu.fixture()
+    tr = gio.Transitions('steps.npz')
+    feats = gio.Features()
+    mods = {k: _module(k) for k in fx}
+    step = 1
+    n = 0
+    worst32 = worst64 = 0.0
+    with torch.no_grad():
+        for i in range(0, tr.n, step):
+            name = qu.kind(int(tr.z['nships'][i]))
+            for s, f in _golden_features(tr, feats, i):
+                got = mods[name](torch.from_numpy(np.ascontiguousarray(f))).numpy()
+                e32 = np.abs(got.astype(np.float64) - q32[i, s]).max()
+                e64 = np.abs(qnet.forward64(fx[name]['weights'], f) - q64[i, s]).max()
+                assert e32 <= fx[name]['tol'], (i, s, e32)
+                assert e64 <= 1e-12, (i, s, e64)
+                worst32, worst64 = max(worst32, e32), max(worst64, e64)
+                n += 1
+    print('%d evaluations: torch float32 vs q32 %.3g, forward64 vs q64 %.3g' % (n, worst32, worst64))
+    assert n > 2000
+
+
+def test_value_network_batched_masked_max():
+    """forward on to_batch's -1 padded batches == forward on each state's own rows."""
+    fx, _, q64 = qu.fixture()
+    feats = gio.Features()
+    tr = gio.Transitions('steps.npz')
+    padded = 0
+    for idx, batch in feats.batches():
+        name = qu.kind(int(tr.z['nships'][idx[0]]))
+        nf = 10 if name == 'solo' else 15
+        b = batch[..., :nf]
+        padded += int((b[..., 0] < 0).sum())
+        with torch.no_grad():
+            got = _module(name, torch.float64)(torch.from_numpy(b).double()).numpy()
+        assert np.abs(got - q64[idx, 0]).max() <= 1e-12
+        assert np.abs(qnet.forward64(fx[name]['weights'], b) - q64[idx, 0]).max() <= 1e-12
+    assert padded > 0
+
+
+def test_get_features_matches_fixture():
+    """qnet.get_features == the reference's get_features on golden states
+    (float32 tick-0 bearings and float64 later ones)."""
+    from astro_amd.config import Bodies, State
+    tr = gio.Transitions('steps.npz')
+    feats = gio.Features()
+    z = tr.z
+    seen = set()
+    for i in list(range(0, tr.n, 23)) + list(np.nonzero(z['tick'] == 0)[0][:20]):
+        S, npl, fl = int(z['nships'][i]), int(z['nplanets'][i]), int(z['dtype_flags'][i])
+        sh, pl = z['in_ships'][i, :S], z['in_planets'][i, :npl]
+        bl = z['in_bullets'][z['in_bullets_off'][i]:z['in_bullets_off'][i + 1]]
+        sdt = np.float32 if fl & 1 else np.float64
+        bdt = np.float32 if fl & 8 else np.float64
+        st = State(ships=Bodies(x=sh[:, 0:2].astype(sdt), dx=sh[:, 2:4].astype(sdt), b=sh[:, 4].astype(sdt)),
+                   planets=Bodies(x=pl[:, 0:2].astype(np.float32 if fl & 2 else np.float64),
+                                  dx=pl[:, 2:4].astype(np.float32 if fl & 4 else np.float64), b=None),
+                   bullets=Bodies(x=bl[:, 0:2].astype(bdt), dx=bl[:, 2:4].astype(bdt), b=None), reload=0.0, t=0.0)
+        f = qnet.get_features(st)
+        assert f.dtype == np.float32 and np.array_equal(f, feats.of(i)), i
+        if S == 2:
+            assert np.array_equal(qnet.get_features(core.roll_ships(st, 1)), qnet.swap_ego(feats.of(i))), i
+        seen.add(bool(fl & 1))
+    assert seen == {True, False}
+
+
+def test_qbot_in_core_play(monkeypatch):
+    """QBot in astro_amd.core.play on the config-1 game (DEFAULT_CONFIG, seed
+    42): every tick's control is the argmax of the Q values the bot carries
+    in its data, which are the network's on that tick's ego view.  (The
+    game's physics here is the CPU oracle's create/step behind core.play, so
+    the test needs no device; tests/test_long_games.py plays through the HIP
+    kernel.)"""
+    g = port.Game(DEFAULT_CONFIG)
+    monkeypatch.setattr(core, 'create', lambda config: g.create())
+    monkeypatch.setattr(core, 'step', lambda state, control, config: g.step(state, control))
+    fx, _, _ = qu.fixture()
+    m = _module('duo')
+    bots = [qnet.QBot(m), qnet.QBot(m)]
+    game = core.play(DEFAULT_CONFIG, bots)
+    assert len(game.ticks) > 10
+    picks = set()
+    for k, tick in enumerate(game.ticks):
+        for s in range(2):
+            q = tick.bot_data[s]['q']
+            assert q.shape == (6,) and q.dtype == np.float32
+            assert tick.control[s] == np.argmax(q)
+            picks.add(int(tick.control[s]))
+        if k % 50 == 0 or k == len(game.ticks) - 1:
+            for s in range(2):
+                want = qnet.forward64(fx['duo']['weights'], qnet.get_features(core.roll_ships(tick.state, s)))
+                assert np.abs(tick.bot_data[s]['q'] - want).max() <= fx['duo']['tol'], (k, s)
+    assert len(picks) > 1
+    assert game.winner in (None, 0, 1)
+
+
+def test_exploration_rule():
+    """The numpy restatement of astro_qvalues' epsilon-greedy rule: epsilon 0
+    is greedy, epsilon 1 is the RANDOM policy's own draw, and at 0.25 the
+    explored fraction of 60,000 draws is within 5 sigma of the binomial."""
+    n, S = 30000, 2
+    greedy = np.full((n, S), 7, dtype=np.int64)
+    c0, hit0 = qu.explore(greedy, 0.0, 5, 11, 99)
+    assert not hit0.any() and (c0 == 7).all()
+    c1, hit1 = qu.explore(greedy, 1.0, 5, 11, 99)
+    z = qu.random_words(n, S, 5, 11, 99)
+    assert hit1.all() and np.array_equal(c1, ((z >> np.uint64(32)) * np.uint64(6)) >> np.uint64(32))
+    assert set(c1.flatten().tolist()) == set(range(6))
+    c, hit = qu.explore(greedy, 0.25, 5, 11, 99)
+    k, draws = int(hit.sum()), n * S
+    assert draws == 60000
+    assert abs(k - 0.25 * draws) <= 5 * np.sqrt(draws * 0.25 * 0.75), k
+    assert np.array_equal(c[hit], c1[hit]) and (c[~hit] == 7).all()
+    # the explored controls are uniform: each of the six within 5 sigma
+    counts = np.bincount(c[hit], minlength=6)
+    assert (np.abs(counts - k / 6) <= 5 * np.sqrt(k * (1 / 6) * (5 / 6))).all(), counts
+    # sharding: env_offset h, env i == env_offset 0, env h + i
+    assert np.array_equal(qu.random_words(10, S, 100, 11, 99), qu.random_words(110, S, 0, 11, 99)[100:])

@@ -7,8 +7,9 @@ Test infrastructure only.  This script imports DouglasOrr/Astro's own
 ``astro/__init__.py``'s imports of ``rl``/``server`` -- which need the absent
 ``tensorboardX``/``lru`` -- are skipped) and records inputs and outputs of
 ``core.create`` (core.py:86-135), ``core.generate_configs`` (core.py:77-83) and
-``core.step`` (core.py:215-303), and ``rl.ValueNetwork.get_features`` /
-``to_batch`` (rl.py:36-112), as small ``.npz``/``.json`` fixtures.
+``core.step`` (core.py:215-303), ``rl.ValueNetwork.get_features`` /
+``to_batch`` (rl.py:36-112) and ``rl.ValueNetwork.forward`` (rl.py:137-155),
+as small ``.npz``/``.json`` fixtures.
 
 It refuses to run when ``/root/reference`` is absent, so it never runs on the
 GPU box; the fixtures it writes are plain data (inputs + expected outputs) and
@@ -525,6 +526,85 @@ def gen_features():
 
 
 # ---------------------------------------------------------------------------
+# 6b. Q values: rl.ValueNetwork.forward (rl.py:137-155) of every ship's ego
+#     view of every input state of steps.npz, for one duo and one solo network
+
+def _steps_state(z, i):
+    """Input state i of steps.npz as a reference State (gen_features' rule)."""
+    S = int(z['nships'][i])
+    npl = int(z['nplanets'][i])
+    fl = int(z['dtype_flags'][i])
+    sh = z['in_ships'][i, :S]
+    pl = z['in_planets'][i, :npl]
+    off = z['in_bullets_off']
+    bl = z['in_bullets'][off[i]:off[i + 1]]
+    f32 = np.float32
+    sdt = f32 if fl & 1 else np.float64
+    bdt = f32 if fl & 8 else np.float64
+    B = core.Bodies
+    return core.State(
+        ships=B(x=sh[:, 0:2].astype(sdt), dx=sh[:, 2:4].astype(sdt), b=sh[:, 4].astype(sdt)),
+        planets=B(x=pl[:, 0:2].astype(f32 if fl & 2 else np.float64),
+                  dx=pl[:, 2:4].astype(f32 if fl & 4 else np.float64), b=None),
+        bullets=B(x=bl[:, 0:2].astype(bdt), dx=bl[:, 2:4].astype(bdt), b=None),
+        reload=0.0, t=0.0)
+
+
+def _forward64(w, x):
+    """ValueNetwork.forward of one state's features [rows, nf] in float64
+    (w: state_dict name -> array)."""
+    softsign = lambda a: a / (1.0 + np.abs(a))  # noqa: E731
+    lin = lambda a, k: a @ w[k + '.weight'].astype(np.float64).T + w[k + '.bias'].astype(np.float64)  # noqa: E731
+    h = lin(x.astype(np.float64), 'f0')
+    for k in ('f.0', 'f.1'):
+        h = lin(softsign(h), k)
+    v = h.max(0)
+    for k in ('v.0', 'v.1'):
+        v = softsign(lin(v, k))
+    return np.tanh(lin(v, 'v0'))
+
+
+def gen_qnet():
+    import torch
+    rl = _import_rl()
+    z = load_fixture('steps.npz')
+    n = z['tick'].shape[0]
+    out = dict(torch=np.array(torch.__version__), numpy=np.array(np.__version__))
+    nets = {}
+    for solo in (False, True):
+        torch.manual_seed(7)
+        net = rl.ValueNetwork(solo, 6)
+        with torch.no_grad():
+            for p in net.parameters():
+                p.mul_(3.0)
+        name = 'solo' if solo else 'duo'
+        w = {k: v.numpy().copy() for k, v in net.state_dict().items()}
+        for k, v in w.items():
+            assert v.dtype == np.float32
+            out['%s__%s' % (name, k)] = v
+        nets[name] = (net, w)
+    q32 = np.zeros((n, 2, 6), dtype=np.float32)
+    q64 = np.zeros((n, 2, 6), dtype=np.float64)
+    err = dict(duo=0.0, solo=0.0)
+    for i in range(n):
+        S = int(z['nships'][i])
+        name = 'solo' if S == 1 else 'duo'
+        net, w = nets[name]
+        state = _steps_state(z, i)
+        for s in range(S):
+            ego = core.roll_ships(state, s)
+            with torch.no_grad():
+                a = net.evaluate(ego).data.numpy()
+            b = _forward64(w, rl.ValueNetwork.get_features(ego))
+            assert a.dtype == np.float32 and a.shape == (6,)
+            q32[i, s], q64[i, s] = a, b
+            err[name] = max(err[name], float(np.abs(a.astype(np.float64) - b).max()))
+    out.update(q32=q32, q64=q64, e_ref_duo=np.float64(err['duo']), e_ref_solo=np.float64(err['solo']))
+    np.savez_compressed(os.path.join(OUT, 'qnet.npz'), **out)
+    print('wrote qnet.npz', n, 'states, e_ref', err)
+
+
+# ---------------------------------------------------------------------------
 # 7. A game log written by the reference (core.save_log, core.py:413-426)
 
 def gen_log():
@@ -677,6 +757,9 @@ def generate():
     if sys.argv[1:] == ['features']:
         gen_features()
         return
+    if sys.argv[1:] == ['qnet']:
+        gen_qnet()
+        return
     if sys.argv[1:] == ['log']:
         gen_log()
         return
@@ -691,6 +774,7 @@ def generate():
     gen_steps()
     gen_games()
     gen_features()
+    gen_qnet()
     gen_log()
     gen_script_controls()
     gen_config1()
