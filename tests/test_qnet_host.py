@@ -255,3 +255,64 @@ def test_exploration_rule():
     assert (np.abs(counts - k / 6) <= 5 * np.sqrt(k * (1 / 6) * (5 / 6))).all(), counts
     # sharding: env_offset h, env i == env_offset 0, env h + i
     assert np.array_equal(qu.random_words(10, S, 100, 11, 99), qu.random_words(110, S, 0, 11, 99)[100:])
+
+
+@pytest.mark.parametrize('name', ['solo', 'mp3', 'short'])
+def test_q64_of_batch_reproduces_fixture(name):
+    """tests/qnet_util.py's host reference (oracle.features.batched, swap_ego,
+    forward64) on golden states == the fixture's q64 to 1e-12, and its e_ref
+    (the project's float32 ValueNetwork on the CPU) is the fixture's to within
+    the fixture's tolerance."""
+    fx, _, q64 = qu.fixture()
+    tr = gio.Transitions('steps.npz')
+    idx = dict(tr.groups())[name]
+    S = 1 if gio.configs()[name].solo else 2
+    net = fx[qu.kind(S)]
+    B = tr.batch_in(idx, S, b_cap=tr.max_bullets(idx) + 2)
+    got = qu.q64_of_batch(net['weights'], B, S)
+    assert got.shape == (idx.size, S, 6) and got.dtype == np.float64
+    assert np.abs(got - q64[idx, :S]).max() <= 1e-12
+    q2, e = qu.reference_of(net['weights'], B, S)
+    assert np.array_equal(q2, got) and e == qu.e_ref_of(net['weights'], B, S)
+    assert 0.0 < e <= net['e_ref'] + net['tol']
+    # fewer outputs: the first rows of v0
+    w3 = dict(net['weights'])
+    w3['v0.weight'], w3['v0.bias'] = w3['v0.weight'][:3], w3['v0.bias'][:3]
+    assert np.abs(qu.q64_of_batch(w3, B.take(np.arange(50)), S) - q64[idx[:50], :S, :3]).max() <= 1e-12
+
+
+@pytest.mark.parametrize('S', [1, 2])
+def test_synthetic_batch_round_trip(S):
+    """synthetic_batch's states come back from oracle.features.batched with
+    the requested counts and their own float32-representable values."""
+    from oracle import features
+    rng = np.random.RandomState(1)
+    counts = [(1, 0), (16, 0), (3, 70), (1, 1), (7, 33), (16, 5)]
+    rows = max(a + b for a, b in counts)
+    for tick, bearings in ((0, None), (5, None), (5, np.arange(len(counts) * S).reshape(-1, S) * 0.75 - 3.0)):
+        B = qu.synthetic_batch(counts, S, 16, rng, tick, bearings)
+        assert B.bullets.shape == (len(counts), 70, 4) and B.planets.shape == (len(counts), 16, 4)
+        assert (B.tick == tick).all()
+        for a in (B.ships, B.ships_b):
+            assert np.array_equal(a, a.astype(np.float32).astype(np.float64))
+            assert np.isfinite(a).all()
+        assert np.abs(B.ships).max() <= 1.2 and np.abs(B.ships_b).max() <= 10.0
+        if bearings is not None:
+            assert np.array_equal(B.ships_b, bearings)
+        f = features.batched(B, S, rows=rows)
+        assert f.shape == (len(counts), rows, 5 + 5 * S) and not np.isnan(f).any()
+        for i, (npl, nb) in enumerate(counts):
+            assert (f[i, :npl, 0] == 0).all() and (f[i, npl:npl + nb, 0] == 1).all() and (f[i, npl + nb:] == -1).all()
+            assert np.array_equal(f[i, :npl, -4:].astype(np.float64), B.planets[i, :npl])
+            assert np.array_equal(f[i, npl:npl + nb, -4:].astype(np.float64), B.bullets[i, :nb])
+            assert np.abs(f[i, :npl + nb, -4:]).max() <= 1.2
+            assert np.array_equal(f[i, 0, 1:5].astype(np.float64), B.ships[i, 0])
+            assert np.isnan(B.planets[i, npl:]).all() and np.isnan(B.bullets[i, nb:]).all()
+        # the views: ego 1 sees the ships exchanged, the objects unchanged
+        v = qu.batch_views(B, S)
+        assert len(v) == S and np.array_equal(v[0], f)
+        if S == 2:
+            assert np.array_equal(v[1][..., 1:6], f[..., 6:11]) and np.array_equal(v[1][..., 11:], f[..., 11:])
+    for bad in ([(0, 1)], [(17, 0)], [(1, -1)]):
+        with pytest.raises(ValueError):
+            qu.synthetic_batch(bad, S, 16, rng, 0)
