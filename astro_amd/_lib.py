@@ -1,5 +1,6 @@
-"""ctypes binding of libastro_hip.so (include/astro_step.h) and of
-libastro_qnet.so (include/astro_qnet.h).
+"""ctypes binding of libastro_hip.so (include/astro_step.h), of
+libastro_qnet.so (include/astro_qnet.h) and of libastro_qtrain.so
+(include/astro_qtrain.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -180,8 +181,23 @@ _QNET_SYMBOLS = {
                                      ctypes.POINTER(AstroPolicy), ctypes.c_double, ctypes.c_void_p]),
 }
 
+# libastro_qtrain.so: the training half, again a library of its own (include/astro_qtrain.h)
+QTRAIN_LIB_PATH = os.environ.get('ASTRO_QTRAIN_LIB') or os.path.join(HERE, 'libastro_qtrain.so')
+QTRAIN_ABI_VERSION = 1
+_QTRAIN_SYMBOLS = {
+    'astro_qtrain_abi_version': (ctypes.c_int, []),
+    'astro_qtrain_last_error': (ctypes.c_char_p, []),
+    'astro_qforward': (ctypes.c_int, [ctypes.POINTER(AstroQNet), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'astro_qgrad_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(AstroQNet), ctypes.c_int32]),
+    'astro_qgrad': (ctypes.c_int, [ctypes.POINTER(AstroQNet), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+}
+
 _lib = None
 _qnet_lib = None
+_qtrain_lib = None
 
 
 class AstroError(RuntimeError):
@@ -245,4 +261,31 @@ def load_qnet(path=QNET_LIB_PATH):
 def check_qnet(rc, what):
     if rc != 0:
         msg = load_qnet().astro_qnet_last_error().decode(errors='replace')
+        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
+
+
+def load_qtrain(path=QTRAIN_LIB_PATH):
+    """Load (once) and type libastro_qtrain.so.  Raises if it is absent or stale."""
+    global _qtrain_lib
+    if _qtrain_lib is not None:
+        return _qtrain_lib
+    if not os.path.exists(path):
+        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
+                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in _QTRAIN_SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.astro_qtrain_abi_version()
+    if v != QTRAIN_ABI_VERSION:
+        raise AstroError('libastro_qtrain.so ABI %d != expected %d (rebuild)' % (v, QTRAIN_ABI_VERSION))
+    _qtrain_lib = lib
+    return lib
+
+
+def check_qtrain(rc, what):
+    if rc != 0:
+        msg = load_qtrain().astro_qtrain_last_error().decode(errors='replace')
         raise AstroError('%s failed (%d): %s' % (what, rc, msg))

@@ -8,7 +8,11 @@ fused into one HIP kernel (csrc/astro_qnet.hip, include/astro_qnet.h).
 * ``QNetwork.from_module(module, device)`` packs its weights into the device
   buffer ``BatchedEnv.qvalues`` / ``qcontrols`` / ``rollout_q`` take: the
   kernel reads the env state directly, so acting needs no feature tensor.
-* ``forward64`` is the same forward pass in numpy float64 (the tests' truth);
+* ``QNetwork.forward`` / ``qmax`` / ``td_targets`` / ``grad`` / ``sgd_step``
+  train the packed buffer in place on the device (csrc/astro_qtrain.hip,
+  include/astro_qtrain.h): rl.QNetworkTrainer.step without a torch module.
+* ``forward64`` is the same forward pass in numpy float64 (the tests' truth),
+  ``grad64`` its backward pass;
   ``QBot`` is the reference's evaluation bot for the single-game
   ``astro_amd.core.play``, on the host.
 """
@@ -151,9 +155,72 @@ def forward64(weights, features):
     return np.tanh(lin(v, 'v0'))
 
 
+def grad64(weights, features, action, target):
+    """rl.QNetworkTrainer.step's loss and gradient (rl.py:184-188) in numpy
+    float64: y = Q(features)[action], loss = (target - y)^2, L = mean(loss).
+    features [n, rows, nf] with to_batch's padding (column 0 < 0, anywhere
+    among the rows; a padding row's other columns are ignored).  The pool's
+    gradient goes to the first maximal live row (np.argmax).  A sample whose
+    action is outside [0, nout) has loss NaN and adds nothing, but counts in
+    the mean.  Returns (loss [n], {state_dict name: dL/dw})."""
+    w = {k: v.astype(np.float64) for k, v in _arrays(weights).items()}
+    x = np.asarray(features, dtype=np.float64)
+    n, nout = x.shape[0], w['v0.weight'].shape[0]
+    live = ~(x[..., 0] < 0)
+    x = np.where(live[..., None], x, 0.0)
+    action = np.asarray(action).astype(np.int64).reshape(n)
+    target = np.asarray(target, dtype=np.float64).reshape(n)
+
+    def fwd(a, k):   # softsign(linear): (value, reciprocal of 1 + |z|)
+        z = a @ w[k + '.weight'].T + w[k + '.bias']
+        r = 1.0 / (1.0 + np.abs(z))
+        return z * r, r
+
+    a0, r0 = fwd(x, 'f0')
+    a1, r1 = fwd(a0, 'f.0')
+    z2 = a1 @ w['f.1.weight'].T + w['f.1.bias']
+    arg = np.where(live[..., None], z2, -np.inf).argmax(1)            # [n, 32]: the first maximal live row
+    p = np.take_along_axis(z2, arg[:, None, :], 1)[:, 0, :]
+    av0, rv0 = fwd(p, 'v.0')
+    av1, rv1 = fwd(av0, 'v.1')
+    q = np.tanh(av1 @ w['v0.weight'].T + w['v0.bias'])
+    ok = (action >= 0) & (action < nout)
+    a = np.where(ok, action, 0)
+    y = q[np.arange(n), a]
+    loss = np.where(ok, (target - y) ** 2, np.nan)
+
+    g = {}
+
+    def bwd(k, dz, inp):   # a linear layer's parameter gradients; returns the input's gradient
+        g[k + '.weight'] = dz.reshape(-1, dz.shape[-1]).T @ inp.reshape(-1, inp.shape[-1])
+        g[k + '.bias'] = dz.reshape(-1, dz.shape[-1]).sum(0)
+        return dz @ w[k + '.weight']
+
+    dz = np.zeros((n, nout))
+    dz[np.arange(n), a] = np.where(ok, 2.0 * (y - target) / max(n, 1) * (1.0 - y * y), 0.0)
+    dz = bwd('v0', dz, av1) * rv1 ** 2
+    dz = bwd('v.1', dz, av0) * rv0 ** 2
+    dp = bwd('v.0', dz, p)
+    dz = np.zeros_like(z2)
+    np.put_along_axis(dz, arg[:, None, :], dp[:, None, :], 1)
+    dz = bwd('f.1', dz, a1) * r1 ** 2
+    dz = bwd('f.0', dz, a0) * r0 ** 2
+    bwd('f0', dz, x)
+    return loss, {k: g[k] for k, _ in shapes((x.shape[-1] - 5) // 5, nout)}
+
+
+def _td_targets(reward, discount, qmax, terminal):
+    """rl.QBotTrainer._step's targets (rl.py:281-291) from max_a Q(new_state_f)."""
+    return torch.where(terminal.to(torch.bool), reward, discount * qmax)
+
+
 class QNetwork:
     """A ValueNetwork's weights packed on a device, as astro_qvalues reads
-    them (``BatchedEnv.qvalues(net)``).  A snapshot: pack again after training."""
+    them (``BatchedEnv.qvalues(net)``).  ``sgd_step`` trains the buffer in
+    place, so the acting kernel sees the new weights at once; ``update``
+    copies a torch module's weights in.  ``grad`` and ``sgd_step`` share one
+    cached workspace per QNetwork: issue them on one stream (or order the
+    streams yourself); calls on two streams at once would race on it."""
 
     def __init__(self, flat, nships, nout, device):
         flat = np.ascontiguousarray(flat, dtype=np.float32)
@@ -165,6 +232,7 @@ class QNetwork:
             raise ValueError('QNetwork lives on a HIP device (got %s)' % self.device)
         self.weights = torch.from_numpy(flat).to(self.device)
         self.c = _lib.AstroQNet(weights=self.weights.data_ptr(), nships=self.nships, nout=self.nout)
+        self._workspace = None    # astro_qgrad's scratch, grown when needed
 
     @classmethod
     def from_module(cls, module, device='cuda'):
@@ -184,6 +252,118 @@ class QNetwork:
 
     def byref(self):
         return ctypes.byref(self.c)
+
+    def state_dict(self):
+        """{state_dict name: view into the flat device buffer}: what
+        ``module.load_state_dict`` takes to write the network back into a
+        torch or reference module."""
+        out, k = {}, 0
+        for name, shape in shapes(self.nships, self.nout):
+            size = int(np.prod(shape))
+            out[name] = self.weights[k:k + size].view(shape)
+            k += size
+        return out
+
+    # ------------------------------------------------ training (astro_qtrain.h)
+
+    def _features(self, features):
+        nf = 5 + 5 * self.nships
+        if (not torch.is_tensor(features) or features.dim() != 3 or features.shape[2] != nf
+                or features.shape[1] < 1 or features.dtype != torch.float32
+                or features.device != self.weights.device or not features.is_contiguous()):
+            raise ValueError('features must be a contiguous float32 [n, rows, %d] tensor on %s'
+                             % (nf, self.weights.device))
+        return int(features.shape[0]), int(features.shape[1])
+
+    def _out(self, out, shape, what):
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.weights.device)
+        if (not torch.is_tensor(out) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32
+                or out.device != self.weights.device or not out.is_contiguous()):
+            raise ValueError('%s must be a contiguous float32 %s tensor on %s'
+                             % (what, list(shape), self.weights.device))
+        return out
+
+    def _vector(self, v, n, what):
+        """An [n] input on the device, of any stride (the callers convert, which also packs it)."""
+        if not torch.is_tensor(v) or tuple(v.shape) != (n,) or v.device != self.weights.device:
+            raise ValueError('%s must be a [%d] tensor on %s' % (what, n, self.weights.device))
+        return v
+
+    def _qforward(self, features, q, qmax):
+        n, rows = self._features(features)
+        if n == 0:      # (an empty tensor has no address)
+            return
+        lib = _lib.load_qtrain()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.weights.device).cuda_stream)
+        _lib.check_qtrain(lib.astro_qforward(self.byref(), features.data_ptr(), n, rows,
+                                             None if q is None else q.data_ptr(),
+                                             None if qmax is None else qmax.data_ptr(), stream), 'astro_qforward')
+
+    def forward(self, features, out=None):
+        """rl.ValueNetwork.forward on a to_batch feature tensor
+        (``BatchedEnv.features()``): float32 [n, nout]."""
+        n, _ = self._features(features)
+        q = self._out(out, (n, self.nout), 'out')
+        self._qforward(features, q, None)
+        return q
+
+    def qmax(self, features, out=None):
+        """The maximum of ``forward(features)`` over the outputs: float32 [n]."""
+        n, _ = self._features(features)
+        m = self._out(out, (n,), 'out')
+        self._qforward(features, None, m)
+        return m
+
+    def td_targets(self, reward, discount, next_features, terminal):
+        """rl.QBotTrainer._step's targets (rl.py:281-291): ``reward`` where
+        ``terminal``, ``discount * max_a Q(next_features)`` elsewhere (a
+        terminal sample's next_features may hold anything).  reward, terminal:
+        [n] tensors on the device; discount: a number or an [n] tensor."""
+        n, _ = self._features(next_features)
+        reward = self._vector(reward, n, 'reward').to(torch.float32)
+        return _td_targets(reward, discount, self.qmax(next_features), self._vector(terminal, n, 'terminal'))
+
+    def grad(self, features, action, target, loss_out=None, grad_out=None):
+        """rl.QNetworkTrainer.step's loss and gradient (rl.py:184-188): y =
+        Q(features)[action], loss = (target - y)^2, L = mean(loss).  action:
+        an integer [n] tensor, target: float32 [n].  Returns (loss [n], dL/dw
+        [nparams] in the layout of ``weights``); deterministic bit for bit.
+        Stream-ordered on the current stream; see the class on the shared
+        workspace."""
+        n, rows = self._features(features)
+        action = self._vector(action, n, 'action')
+        if action.dtype.is_floating_point or action.dtype == torch.bool:
+            raise ValueError('action must be an integer tensor')
+        if action.dtype != torch.int8:
+            # widened first (an unsigned dtype cannot hold the -1 bound), then clamped so that a
+            # value outside int8 stays out of range instead of wrapping into it
+            action = action.to(torch.int64).clamp(-1, 127).to(torch.int8)
+        action = action.contiguous()
+        target = self._vector(target, n, 'target')
+        if target.dtype != torch.float32:
+            raise ValueError('target must be a float32 tensor')
+        target = target.contiguous()
+        loss = self._out(loss_out, (n,), 'loss_out')
+        grad = self._out(grad_out, (self.weights.numel(),), 'grad_out')
+        lib = _lib.load_qtrain()
+        need = int(lib.astro_qgrad_workspace_bytes(self.byref(), n))
+        ws = self._workspace
+        if ws is None or ws.numel() * 4 < need:
+            ws = self._workspace = torch.empty(max(1, (need + 3) // 4), dtype=torch.float32,
+                                               device=self.weights.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.weights.device).cuda_stream)
+        _lib.check_qtrain(lib.astro_qgrad(self.byref(), features.data_ptr(), n, rows, action.data_ptr(),
+                                          target.data_ptr(), loss.data_ptr(), grad.data_ptr(), ws.data_ptr(),
+                                          ws.numel() * 4, stream), 'astro_qgrad')
+        return loss, grad
+
+    def sgd_step(self, features, action, target, lr=1e-2):
+        """rl.QNetworkTrainer.step (rl.py:176-192, SGD with lr 1e-2) on the
+        packed buffer, in place.  Returns the per-sample loss [n]."""
+        loss, grad = self.grad(features, action, target)
+        self.weights.add_(grad, alpha=-lr)
+        return loss
 
 
 class QBot:
