@@ -508,6 +508,19 @@ __device__ __forceinline__ bool seed_passes(const AstroParams &p, uint32_t seed,
 constexpr double TWO_PI = 6.283185307179586;  // 2 * np.pi
 constexpr double PI = 3.141592653589793;      // np.pi
 
+// create()'s two values that depend on the config and the planet count alone
+// (core.py:113, 121):
+//   stp = 2 pi / n                                    the angle between planets
+//   amp = sqrt(gravity * planet_mass * (n - 1) / 2)   the planets' orbital speed
+// With planets_only > 1 every game a reset pass creates has that many planets,
+// known before the launch: the host makes the two values for it
+// (uniform_create_of: the reference's operation order in IEEE double) and the
+// quad/pair kernels take them by value, so the pair helpers' pass runs no
+// float64 division or sqrt and no select on n.  (Zero otherwise: unused.)
+struct UniformCreate {
+    double stp, amp;
+};
+
 // ---------------------------------------------------------------------------
 // The random draws of create() (core.py:88-116), in the reference's order:
 // randint(1, max_planets + 1), rand(2) (outer), rand() (inner), rand() (ship
@@ -1642,14 +1655,17 @@ __device__ __forceinline__ typename Store<T>::V create_ship(const AstroParams &p
 }
 
 // planet j of an n-planet game: position angle (sn, cs), velocity angle (vs, vc)
-template <typename T>
+// (UNI: n is planets_only > 1 and amp_u the host-made speed)
+template <typename T, bool UNI = false>
 __device__ __forceinline__ typename Store<T>::V create_planet(const AstroParams &p, int n, float sn, float cs,
-                                                             float vs, float vc) {
+                                                             float vs, float vc, double amp_u = 0.0) {
     typename Store<T>::V v;
     if (n <= 1) {
         v.x = v.y = v.z = v.w = T(0);
     } else {
-        const double amp = sqrt(p.gravity * p.planet_mass * double(n - 1) / 2.0);
+        double amp;
+        if constexpr (UNI) amp = amp_u;
+        else amp = sqrt(p.gravity * p.planet_mass * double(n - 1) / 2.0);
         v.x = T(p.planet_orbit * sn);
         v.y = T(p.planet_orbit * cs);
         v.z = T(amp * double(vs));
@@ -1665,14 +1681,18 @@ __device__ __forceinline__ typename Store<T>::V create_planet(const AstroParams 
 // results move by shuffles; lane s < S writes ship s, lane j < n planet j
 // (same arithmetic as create_env, bit for bit).  All lanes of the row must
 // be active; `write` gates the stores.
-template <typename T, int S, int PMAX, class Sink>
+// UNI: d.n is planets_only > 1 (wave-uniform) and uc its host-made constants.
+template <typename T, int S, int PMAX, class Sink, bool UNI = false>
 __device__ __forceinline__ int create_env_row(const AstroParams &p, const Sink &sink, int ie,
-                                              const CreateDraws<S> &d, int u, int row0, bool write) {
+                                              const CreateDraws<S> &d, int u, int row0, bool write,
+                                              const UniformCreate &uc = UniformCreate{}) {
     static_assert(2 * PMAX <= 16, "one planet angle per lane of a 16-lane row");
     constexpr bool INNER_LANE = 2 * PMAX + 1 <= 16;   // the inner ship angle on lane 2 PMAX
     using V = typename Store<T>::V;
     int n = d.n;
-    const double stp = TWO_PI / double(n);
+    double stp;
+    if constexpr (UNI) stp = uc.stp;
+    else stp = TWO_PI / double(n);
     const double base = TWO_PI * d.u_base;
     const double turn = double(d.reverse) * PI / 2.0;
     const int j = u < PMAX ? u : (u < 2 * PMAX ? u - PMAX : 0);
@@ -1696,7 +1716,7 @@ __device__ __forceinline__ int create_env_row(const AstroParams &p, const Sink &
     if (write && u < S) sink.ship(u, ie, sv, b);
     // planets (core.py:111-121): lane j < n writes planet j
     if (write && u < PMAX) {
-        const V v = create_planet<T>(p, n, sn, cs, vs, vc);
+        const V v = create_planet<T, UNI>(p, n, sn, cs, vs, vc, uc.amp);
         if (u < n) sink.planet(u, 0, ie, v);
     }
     if (n > PMAX) n = PMAX;
@@ -1716,13 +1736,20 @@ __device__ __forceinline__ int create_env_row(const AstroParams &p, const Sink &
 // create, and so is one whose game ended at its first step (its seed still
 // UNDRAWN).  The stream cursor is left alone: the next game's seed is drawn
 // by the env's first step.  Returns the leaders not yet served.
-template <typename T, int S, int PMAX, int LPE, bool PRE = false, class Sink = GlobalSink<T>>
+template <typename T, int S, int PMAX, int LPE, bool PRE = false, class Sink = GlobalSink<T>, bool UNI_K = false>
 __device__ __forceinline__ uint64_t wave_reset_pass(const AstroParams &p, const AstroState &st, uint64_t todo,
                                                     int lane, int i, uint32_t pend_seed, uint32_t pend_key,
                                                     bool have_key, bool undrawn, uint32_t (*s_chain)[2][13 + 2 * S],
                                                     int *s_serial, const Sink &sink_all STAMP_ARG,
-                                                    const uint32_t (*pre)[2][13 + 2 * S] = nullptr) {
+                                                    const uint32_t (*pre)[2][13 + 2 * S] = nullptr,
+                                                    int base_env = 0, uint64_t undrawn_mask = 0,
+                                                    const UniformCreate &uc = UniformCreate{}) {
     constexpr int NW = 12 + 2 * S;   // outputs create() draws, randint accepting its first word
+    // The pair helpers' pass (the tail of c3's one-tick launch) is the lean one:
+    // no shuffle from the leader lanes, and with planets_only > 1 no select
+    // on n and no float64 division or sqrt.  Every other instance keeps the
+    // general form: there the same changes were even or lost
+    constexpr bool LEAN = PRE && LPE == 2;
     int leader[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {   // uniform
@@ -1733,13 +1760,27 @@ __device__ __forceinline__ uint64_t wave_reset_pass(const AstroParams &p, const 
     const int L = row == 0 ? leader[0] : row == 1 ? leader[1] : row == 2 ? leader[2] : leader[3];
     const bool on = L >= 0;
     const int src = on ? L : 0;
-    const int ie = __shfl(i, src, 64);
-    const uint32_t seed = uint32_t(__shfl(int(pend_seed), src, 64));
-    const uint32_t key = uint32_t(__shfl(int(pend_key), src, 64));
-    const bool hk = __shfl(int(have_key), src, 64) != 0;
-    const bool ud = __shfl(int(undrawn), src, 64) != 0;
-
     const int uw = u < NW ? u : 0;
+    int ie;
+    uint32_t seed, key = 0;
+    bool hk = false, ud;
+    if constexpr (LEAN) {
+        // nothing comes from the leader lane by a shuffle: a leader is an
+        // active lane, so its env is base_env + src / LPE; the seed is the
+        // first word of the env's seed chain (lane u == 0 reads it as a0
+        // below, the one lane that stores it); the key is in the chains
+        // already; `undrawn` is a bit of the caller's ballot
+        ie = base_env + src / LPE;
+        seed = pre[src / LPE][0][uw];
+        ud = (undrawn_mask >> src) & 1ull;
+    } else {
+        ie = __shfl(i, src, 64);
+        seed = uint32_t(__shfl(int(pend_seed), src, 64));
+        key = uint32_t(__shfl(int(pend_key), src, 64));
+        hk = __shfl(int(have_key), src, 64) != 0;
+        ud = __shfl(int(undrawn), src, 64) != 0;
+    }
+
     uint32_t a0, a1, b0;
     if constexpr (PRE) {   // the env's two chains, made ahead (a helper wave, HelpBox)
         const int le = src / LPE;
@@ -1782,9 +1823,13 @@ __device__ __forceinline__ uint64_t wave_reset_pass(const AstroParams &p, const 
     // lane k of the row: R_k = rand() of outputs k, k + 1
     const uint32_t wn = uint32_t(row_from_i<1>(int(w)));
     const double R = rand53(w, wn);
+    // UNI_K: the instance launched when planets_only > 1 (a fast game then has
+    // planets_only planets); an instance of its own, so neither carries the
+    // other's create (both in one kernel cost c3any 0.03 us, ab_c3any_9rounds.jsonl)
+    constexpr bool uni = LEAN && UNI_K;
     CreateDraws<S> d;
-    d.n = 1 + int(v);
-    const bool many = d.n > 1;
+    d.n = uni ? p.planets_only : 1 + int(v);
+    const bool many = uni || d.n > 1;
     d.u_out[0] = row_bcast<1>(R);
     d.u_out[1] = row_bcast<3>(R);
     d.u_inner = row_bcast<5>(R);
@@ -1804,7 +1849,8 @@ __device__ __forceinline__ uint64_t wave_reset_pass(const AstroParams &p, const 
     const Sink sink = sink_all.for_row(row);   // where row `row`'s game goes
     int n, cf = 0;
     if constexpr (2 * PMAX <= 16) {
-        n = create_env_row<T, S, PMAX>(p, sink, ie, d, u, row0, on && fast);
+        if constexpr (uni) n = create_env_row<T, S, PMAX, Sink, true>(p, sink, ie, d, u, row0, on && fast, uc);
+        else n = create_env_row<T, S, PMAX>(p, sink, ie, d, u, row0, on && fast);
     } else {
         if (on && fast) n = create_env<T, S, PMAX, 16, Sink>(p, sink, ie, d, cf, u);
     }
@@ -2496,10 +2542,11 @@ __device__ __forceinline__ void bullets_rounds(const AstroParams &p, const BM &b
 }
 
 template <typename T, int S, int PMAX, int LPE, bool OPAQUE = false, bool BOTS = false, bool HELP = false,
-          int WPG = QW>
+          int WPG = QW, bool UNI_K = false>
 __device__ __forceinline__ QuadCounts quad_tick(const AstroParams &p, const AstroState &st, const TickDriver &drv,
                                                 float *__restrict__ reward_all, uint8_t *__restrict__ done_all,
-                                                bool stats, int auto_reset, int kt STAMP_ARG) {
+                                                bool stats, int auto_reset, int kt,
+                                                const UniformCreate &uni_c STAMP_ARG) {
     using V = typename Store<T>::V;
     constexpr int PPL = PMAX / LPE;   // planet slots per lane
     constexpr int QENV = 64 / LPE;    // envs per wave
@@ -2649,6 +2696,8 @@ __device__ __forceinline__ QuadCounts quad_tick(const AstroParams &p, const Astr
             np = np < 1 ? 1 : (np > PMAX ? PMAX : np);
             const bool t0 = (uint32_t(hh.x) & TICK_MASK) == 0;
             const bool slot_last = __builtin_amdgcn_readfirstlane(int(__any(np == PMAX))) != 0;
+            const uint64_t hud_mask = __ballot(hud);
+            const UniformCreate huc = uni_c;   // (kernarg scalars, here ahead of the wait)
             V hpv[PPL], hout[PPL];
             T hpx[PPL], hpy[PPL];
             if constexpr (PLANETS) {
@@ -2701,8 +2750,9 @@ __device__ __forceinline__ QuadCounts quad_tick(const AstroParams &p, const Astr
             HSTAMP_T(28);
             if (todo0) {   // uniform
                 for (uint64_t todo = todo0; todo;)   // uniform
-                    todo = wave_reset_pass<T, S, PMAX, LPE, true>(p, st, todo, lane, i, hseed, hkey, hk, hud, s_chain,
-                                                                  s_serial, GlobalSink<T>{st} STAMP_PASS, pre);
+                    todo = wave_reset_pass<T, S, PMAX, LPE, true, GlobalSink<T>, UNI_K>(p, st, todo, lane, i, hseed, hkey, hk, hud, s_chain,
+                                                                  s_serial, GlobalSink<T>{st} STAMP_PASS, pre, base,
+                                                                  hud_mask, huc);
                 HSTAMP_T(29);
 #ifdef ASTRO_STAMPS
                 stamp_[32] = stamp_[16];
@@ -3206,26 +3256,35 @@ typedef const __attribute__((address_space(4))) QuadArgs *KernArgs;
 #endif
 constexpr int P8_WAVES = ASTRO_P8_WAVES, P4_WAVES = ASTRO_P4_WAVES, M4_WAVES = ASTRO_M4_WAVES;
 
+// The step wave whose stats row a wave of the workgroup adds to: its own, or
+// for a helper wave the one it serves (quad_tick's wv: the helper shift)
+template <bool HELP, int WPG>
+__device__ __forceinline__ int stats_wave() {
+    const int w = int(threadIdx.x >> 6);
+    return HELP && w >= WPG ? (w - WPG + ASTRO_HELPER_SHIFT) % WPG : w % WPG;
+}
+
 // STATS: the one-tick instances come in two builds, with the counters and
 // without (a launch with a null stats pointer): compiled in but switched off
 // at run time they still cost c3 0.6 us per launch, switched on 1.6 us of
 // 12.1 (the per-lane counts, the wave sums and the row atomics at the
 // slowest waves' ends; profiles/round5/ab_stats_flush.jsonl)
 template <typename T, int S, int PMAX, bool MULTI, int LPE, bool BOTS = false, bool HELP = false,
-          int WPG = QW, bool STATS = true>
+          int WPG = QW, bool STATS = true, bool UNI_K = false>
 __global__ __launch_bounds__(HELP ? 2 * (64 * WPG) : (64 * WPG), MULTI ? (BOTS || PMAX > 4 ? 2 : M4_WAVES) : (PMAX > 4 ? P8_WAVES : P4_WAVES)) void astro_step_quad_kernel(AstroParams p, AstroState st, TickDriver drv,
                                                                 float *__restrict__ reward_all,
                                                                 uint8_t *__restrict__ done_all,
-                                                                unsigned long long *stats, int auto_reset) {
+                                                                unsigned long long *stats, int auto_reset,
+                                                                UniformCreate uni) {
 #ifdef ASTRO_STAMPS
     unsigned long long stamp_[NSTAMP] = {};
-    quad_tick<T, S, PMAX, LPE, false, false, HELP, WPG>(p, st, drv, reward_all, done_all, STATS && stats != nullptr,
-                                                       auto_reset, 0,
+    quad_tick<T, S, PMAX, LPE, false, false, HELP, WPG, UNI_K>(p, st, drv, reward_all, done_all, STATS && stats != nullptr,
+                                                       auto_reset, 0, uni,
                                                    stamp_);
     STAMP(11);
-    if (stats && (threadIdx.x & 63) == 0) {   // a helper wave: slots 20-22 of its step wave's row
+    if (stats && (threadIdx.x & 63) == 0) {   // a helper wave: slots 20 and up of the row of the step wave it serves
         const bool hw = int(threadIdx.x) >= (64 * WPG);
-        unsigned long long *row = stats + size_t(blockIdx.x * WPG + (threadIdx.x / 64) % WPG) * NSTAMP;
+        unsigned long long *row = stats + size_t(blockIdx.x * WPG + stats_wave<HELP, WPG>()) * NSTAMP;
         // (constant indices only: a loop over a runtime range put the stamp
         // array in scratch, and its stores then sat in the same vmcnt queue
         // as the wave's first loads -- the header wait measured them too)
@@ -3264,13 +3323,13 @@ __global__ __launch_bounds__(HELP ? 2 * (64 * WPG) : (64 * WPG), MULTI ? (BOTS |
             asm volatile("" : "+s"(kp));
             const QuadArgs &a = *(const QuadArgs *)(KernArgs(kp));
             c = quad_tick<T, S, PMAX, LPE, true, BOTS>(a.p, a.st, a.drv, a.reward, a.done, a.stats != nullptr,
-                                                        a.auto_reset, kt);
+                                                        a.auto_reset, kt, UniformCreate{});
         } else {
-            c = quad_tick<T, S, PMAX, LPE, false, false, HELP, WPG>(p, st, drv, reward_all, done_all,
-                                                               STATS && stats != nullptr, auto_reset, kt);
+            c = quad_tick<T, S, PMAX, LPE, false, false, HELP, WPG, UNI_K>(p, st, drv, reward_all, done_all,
+                                                               STATS && stats != nullptr, auto_reset, kt, uni);
         }
         if (STATS && stats) {
-            const int row = __builtin_amdgcn_readfirstlane(int(blockIdx.x * WPG + (threadIdx.x / 64) % WPG));
+            const int row = __builtin_amdgcn_readfirstlane(int(blockIdx.x * WPG + stats_wave<HELP, WPG>()));
             if (row * (64 / LPE) < st.n_env)
                 flush_counts(stats + size_t(row) * ASTRO_NSTATS, c, p.b_cap * (64 / LPE) < 65536);
         }
@@ -4057,9 +4116,24 @@ __host__ inline int late_block_of(const void *fn, int block, int grid) {
     return cap > 0 && grid > cap && grid % cap != 0 ? (grid / cap) * cap : 0;
 }
 
+// create()'s two constants of the planet count planets_only > 1 fixes
+// (UniformCreate; core.py's expressions in its operation order -- this file
+// is built without contraction, and the device's float64 division and sqrt
+// are correctly rounded as well, so both sides make the same bits)
+UniformCreate uniform_create_of(const AstroParams &p) {
+    UniformCreate u{0.0, 0.0};
+    if (p.planets_only > 1) {
+        const int n = p.planets_only;
+        u.stp = TWO_PI / double(n);
+        u.amp = sqrt(p.gravity * p.planet_mass * double(n - 1) / 2.0);
+    }
+    return u;
+}
+
 template <typename T, int S, int PM>
 int launch_step(const AstroParams &p, const AstroState &s, const TickDriver &drv, float *r, uint8_t *d,
                 uint64_t *stats, int ar, hipStream_t stream) {
+    const UniformCreate uni = uniform_create_of(p);
     unsigned long long *st = reinterpret_cast<unsigned long long *>(stats);
 #ifdef ASTRO_STAMPS   // (stamp rows go to `stats`; the one-tick launches stamped are the counter-free ones)
     const bool count = false;
@@ -4075,7 +4149,7 @@ int launch_step(const AstroParams &p, const AstroState &s, const TickDriver &drv
         if (drv.policy == ASTRO_POLICY_BOTS) {   // ScriptBot code lives in its own (pair) instance only
             const int g2 = int((int64_t(s.n_env) * 2 + QBLOCK - 1) / QBLOCK);
             hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, true, 2, true>), dim3(g2), dim3(QBLOCK), 0, stream,
-                               p, s, drv, r, d, st, ar);
+                               p, s, drv, r, d, st, ar, uni);
             return launched("astro_step(pair, bots)");
         }
         // a one-tick launch of at most ASTRO_HELP_MAX_WAVES waves (two per
@@ -4085,19 +4159,22 @@ int launch_step(const AstroParams &p, const AstroState &s, const TickDriver &drv
                 const dim3 g(int((int64_t(s.n_env) * 4 + 64 * QW_SMALL - 1) / (64 * QW_SMALL))), b(2 * 64 * QW_SMALL);
                 if (count)
                     hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 4, false, true, QW_SMALL, true>), g, b,
-                                       0, stream, p, s, drv, r, d, st, ar);
+                                       0, stream, p, s, drv, r, d, st, ar, uni);
                 else
                     hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 4, false, true, QW_SMALL, false>), g,
-                                       b, 0, stream, p, s, drv, r, d, st, ar);
+                                       b, 0, stream, p, s, drv, r, d, st, ar, uni);
             } else {   // (8 planet slots: four, a 16-wave workgroup would cap the 8-slot code at 128 VGPRs)
                 constexpr int W = PM > 4 ? 4 : QW_PAIR_HELP;
                 const dim3 g(int((int64_t(s.n_env) * 2 + 64 * W - 1) / (64 * W))), b(2 * 64 * W);
                 if (count)
                     hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 2, false, true, W, true>), g, b, 0,
-                                       stream, p, s, drv, r, d, st, ar);
+                                       stream, p, s, drv, r, d, st, ar, uni);
+                else if (p.planets_only > 1)   // (the instance whose reset pass knows the planet count)
+                    hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 2, false, true, W, false, true>), g, b,
+                                       0, stream, p, s, drv, r, d, st, ar, uni);
                 else
                     hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 2, false, true, W, false>), g, b, 0,
-                                       stream, p, s, drv, r, d, st, ar);
+                                       stream, p, s, drv, r, d, st, ar, uni);
             }
             return launched(lpe == 4 ? "astro_step(quad, helpers)" : "astro_step(pair, helpers)");
         }
@@ -4122,14 +4199,14 @@ int launch_step(const AstroParams &p, const AstroState &s, const TickDriver &drv
         if (lpe == 4 && one) {
             if (count)
                 hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 4, false, false, QW, true>), dim3(grid),
-                                   dim3(QBLOCK), 0, stream, p, s, drv, r, d, st, ar);
+                                   dim3(QBLOCK), 0, stream, p, s, drv, r, d, st, ar, uni);
             else
                 hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 4, false, false, QW, false>), dim3(grid),
-                                   dim3(QBLOCK), 0, stream, p, s, drv, r, d, st, ar);
+                                   dim3(QBLOCK), 0, stream, p, s, drv, r, d, st, ar, uni);
         }
         else if (lpe == 4)
             hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, true, 4>), dim3(grid), dim3(QBLOCK), 0, stream, p,
-                               s, drv, r, d, st, ar);
+                               s, drv, r, d, st, ar, uni);
         else if (one) {
             constexpr int W = PM > 4 ? QW : QW_PAIR;
             const dim3 g(int((int64_t(s.n_env) * 2 + 64 * W - 1) / (64 * W))), b(64 * W);
@@ -4139,18 +4216,18 @@ int launch_step(const AstroParams &p, const AstroState &s, const TickDriver &drv
                     reinterpret_cast<const void *>(&astro_step_quad_kernel<T, S, PM, false, 2, false, false, W, true>),
                     int(b.x), int(g.x));
                 hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 2, false, false, W, true>), g, b, 0, stream,
-                                   p, s, dl, r, d, st, ar);
+                                   p, s, dl, r, d, st, ar, uni);
             } else {
                 dl.late_block = late_block_of(
                     reinterpret_cast<const void *>(&astro_step_quad_kernel<T, S, PM, false, 2, false, false, W, false>),
                     int(b.x), int(g.x));
                 hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, false, 2, false, false, W, false>), g, b, 0,
-                                   stream, p, s, dl, r, d, st, ar);
+                                   stream, p, s, dl, r, d, st, ar, uni);
             }
         }
         else
             hipLaunchKernelGGL((astro_step_quad_kernel<T, S, PM, true, 2>), dim3(grid), dim3(QBLOCK), 0, stream, p,
-                               s, drv, r, d, st, ar);
+                               s, drv, r, d, st, ar, uni);
         return launched(lpe == 4 ? "astro_step(quad)" : "astro_step(pair)");
     }
     const int grid = (s.n_env + BLOCK - 1) / BLOCK;
