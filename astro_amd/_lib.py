@@ -1,6 +1,6 @@
 """ctypes binding of libastro_hip.so (include/astro_step.h), of
-libastro_qnet.so (include/astro_qnet.h) and of libastro_qtrain.so
-(include/astro_qtrain.h).
+libastro_qnet.so (include/astro_qnet.h), of libastro_qtrain.so
+(include/astro_qtrain.h) and of libastro_replay.so (include/astro_replay.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -195,9 +195,52 @@ _QTRAIN_SYMBOLS = {
                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 
+
+
+class AstroReplay(ctypes.Structure):
+    """include/astro_replay.h AstroReplay: the replay ring's arrays and shape."""
+    _fields_ = [
+        ('features', ctypes.c_void_p),
+        ('action', ctypes.c_void_p),
+        ('reward', ctypes.c_void_p),
+        ('discount', ctypes.c_void_p),
+        ('next', ctypes.c_void_p),
+        ('loss', ctypes.c_void_p),
+        ('wstart', ctypes.c_void_p),
+        ('gpow', ctypes.c_void_p),
+        ('gamma', ctypes.c_double),
+        ('n_env', ctypes.c_int32),
+        ('rows', ctypes.c_int32),
+        ('nships', ctypes.c_int32),
+        ('ticks', ctypes.c_int32),
+        ('n_steps', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+    ]
+
+
+# libastro_replay.so: the experience replay, a library of its own (include/astro_replay.h)
+REPLAY_LIB_PATH = os.environ.get('ASTRO_REPLAY_LIB') or os.path.join(HERE, 'libastro_replay.so')
+REPLAY_ABI_VERSION = 1
+_REPLAY_SYMBOLS = {
+    'astro_replay_abi_version': (ctypes.c_int, []),
+    'astro_replay_last_error': (ctypes.c_char_p, []),
+    'astro_replay_push': (ctypes.c_int, [ctypes.POINTER(AstroReplay), ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+    'astro_replay_sample_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(AstroReplay)]),
+    'astro_replay_sample': (ctypes.c_int, [ctypes.POINTER(AstroReplay), ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.c_void_p]),
+    'astro_replay_gather': (ctypes.c_int, [ctypes.POINTER(AstroReplay), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p]),
+    'astro_replay_update': (ctypes.c_int, [ctypes.POINTER(AstroReplay), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                           ctypes.c_void_p]),
+}
+
 _lib = None
 _qnet_lib = None
 _qtrain_lib = None
+_replay_lib = None
 
 
 class AstroError(RuntimeError):
@@ -288,4 +331,31 @@ def load_qtrain(path=QTRAIN_LIB_PATH):
 def check_qtrain(rc, what):
     if rc != 0:
         msg = load_qtrain().astro_qtrain_last_error().decode(errors='replace')
+        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
+
+
+def load_replay(path=REPLAY_LIB_PATH):
+    """Load (once) and type libastro_replay.so.  Raises if it is absent or stale."""
+    global _replay_lib
+    if _replay_lib is not None:
+        return _replay_lib
+    if not os.path.exists(path):
+        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
+                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in _REPLAY_SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.astro_replay_abi_version()
+    if v != REPLAY_ABI_VERSION:
+        raise AstroError('libastro_replay.so ABI %d != expected %d (rebuild)' % (v, REPLAY_ABI_VERSION))
+    _replay_lib = lib
+    return lib
+
+
+def check_replay(rc, what):
+    if rc != 0:
+        msg = load_replay().astro_replay_last_error().decode(errors='replace')
         raise AstroError('%s failed (%d): %s' % (what, rc, msg))

@@ -8,7 +8,8 @@ Test infrastructure only.  This script imports DouglasOrr/Astro's own
 ``tensorboardX``/``lru`` -- are skipped) and records inputs and outputs of
 ``core.create`` (core.py:86-135), ``core.generate_configs`` (core.py:77-83) and
 ``core.step`` (core.py:215-303), ``rl.ValueNetwork.get_features`` /
-``to_batch`` (rl.py:36-112) and ``rl.ValueNetwork.forward`` (rl.py:137-155),
+``to_batch`` (rl.py:36-112), ``rl.ValueNetwork.forward`` (rl.py:137-155) and
+``rl.QBotTrainer``'s experience bookkeeping (rl.py:249-258, 303-328),
 as small ``.npz``/``.json`` fixtures.
 
 It refuses to run when ``/root/reference`` is absent, so it never runs on the
@@ -744,7 +745,73 @@ def gen_long_games():
     print('wrote long_games.npz', [(r['key'], r['ticks'], r['winner']) for r in index])
 
 
+# ---------------------------------------------------------------------------
+# 11. The learner's experience bookkeeping: rl.QBotTrainer's n-step flush
+#     (rl.py:249-258, 303-328) through core.play, with the optimisation step
+#     (_step) replaced by a no-op so that only the replay list is exercised
+
+def gen_replay():
+    import torch
+    rl = _import_rl()
+    n_steps, games = 7, 3
+    config0 = CONFIGS['short']
+    torch.manual_seed(7)
+    net = rl.ValueNetwork(solo=False, nout=6)
+    trainer = rl.QNetworkTrainer(net, writer=None)
+    bots = [rl.QBotTrainer(trainer, seed=n) for n in range(2)]
+    for b in bots:
+        b.n_steps = n_steps
+        b._step = lambda: None
+    game_ticks, game_reward, game_winner = [], [], []
+    start = [[0], [0]]
+    for config in it.islice(core.generate_configs(config0), games):
+        game = core.play(config, bots)
+        game_ticks.append(len(game.ticks))
+        game_reward.append(np.asarray(game.ticks[-1].reward, dtype=np.float64))
+        game_winner.append(-1 if game.winner is None else game.winner)
+        for s, b in enumerate(bots):
+            assert not b._nstep_buffer and len(b._replay_buffer) == sum(game_ticks)
+            start[s].append(len(b._replay_buffer))
+    out = dict(n_steps=np.int32(n_steps), discount=np.float64(bots[0].discount),
+               game_ticks=np.array(game_ticks, np.int32), game_reward=np.stack(game_reward),
+               game_winner=np.array(game_winner, np.int32), config=np.array(json.dumps(dict(config0._asdict()))))
+    for s, b in enumerate(bots):
+        xps = b._replay_buffer
+        game = np.zeros(len(xps), np.int32)
+        tick = np.zeros(len(xps), np.int32)
+        for g in range(games):
+            game[start[s][g]:start[s][g + 1]] = g
+            tick[start[s][g]:start[s][g + 1]] = np.arange(game_ticks[g])
+        nxt = np.full(len(xps), -1, np.int64)
+        for i, d in enumerate(xps):
+            if d.new_state_f is None:
+                continue
+            hits = [j for j in range(start[s][game[i]], start[s][game[i] + 1])
+                    if xps[j].state_f.shape == d.new_state_f.shape and np.array_equal(xps[j].state_f, d.new_state_f)]
+            later = [j for j in hits if j > i]
+            assert later, (s, i)
+            nxt[i] = later[0]
+        rows = np.array([d.state_f.shape[0] for d in xps], np.int64)
+        off = np.zeros(len(xps) + 1, np.int64)
+        off[1:] = np.cumsum(rows)
+        p = 's%d_' % s
+        out[p + 'game'], out[p + 'tick'] = game, tick
+        out[p + 'action'] = np.array([d.action for d in xps], np.int8)
+        out[p + 'reward'] = np.array([d.reward for d in xps], np.float64)
+        out[p + 'discount'] = np.array([d.discount for d in xps], np.float64)
+        out[p + 'terminal'] = np.array([d.new_state_f is None for d in xps], np.uint8)
+        out[p + 'next'] = nxt
+        out[p + 'state_f'] = np.concatenate([d.state_f for d in xps]).astype(np.float32)
+        out[p + 'state_off'] = off
+        assert all(d.state_f.dtype == np.float32 and np.isinf(d.loss) for d in xps)
+    np.savez_compressed(os.path.join(OUT, 'replay.npz'), **out)
+    print('wrote replay.npz', game_ticks, game_winner, [r.tolist() for r in game_reward])
+
+
 def generate():
+    if sys.argv[1:] == ['replay']:
+        gen_replay()
+        return
     if sys.argv[1:] == ['config1']:
         gen_config1()
         return
@@ -779,6 +846,7 @@ def generate():
     gen_script_controls()
     gen_config1()
     gen_long_games()
+    gen_replay()
 
 
 # No committed file may exceed 1 MiB: a larger fixture is stored as consecutive
