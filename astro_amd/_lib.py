@@ -1,6 +1,7 @@
 """ctypes binding of libastro_hip.so (include/astro_step.h), of
 libastro_qnet.so (include/astro_qnet.h), of libastro_qtrain.so
-(include/astro_qtrain.h) and of libastro_replay.so (include/astro_replay.h).
+(include/astro_qtrain.h), of libastro_replay.so (include/astro_replay.h) and of
+libastro_actor.so (include/astro_actor.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -237,10 +238,55 @@ _REPLAY_SYMBOLS = {
                                            ctypes.c_void_p]),
 }
 
+
+
+class AstroExplore(ctypes.Structure):
+    """include/astro_actor.h AstroExplore: the sticky exploration's state and constants."""
+    _fields_ = [
+        ('policy', ctypes.c_void_p),
+        ('stay_out', ctypes.c_uint64),
+        ('stay_in', ctypes.c_uint64),
+        ('seed', ctypes.c_uint64),
+        ('env_offset', ctypes.c_int64),
+        ('nrandom', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+    ]
+
+
+class AstroEpisodes(ctypes.Structure):
+    """include/astro_actor.h AstroEpisodes: the per-game bookkeeping's arrays."""
+    _fields_ = [
+        ('length', ctypes.c_void_p),
+        ('got', ctypes.c_void_p),
+        ('winner', ctypes.c_void_p),
+        ('ticks', ctypes.c_void_p),
+        ('wins', ctypes.c_void_p),
+        ('finished', ctypes.c_void_p),
+        ('tick_sum', ctypes.c_void_p),
+        ('n_env', ctypes.c_int32),
+        ('nships', ctypes.c_int32),
+        ('games', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+    ]
+
+
+# libastro_actor.so: exploration and episode bookkeeping, a library of its own (include/astro_actor.h)
+ACTOR_LIB_PATH = os.environ.get('ASTRO_ACTOR_LIB') or os.path.join(HERE, 'libastro_actor.so')
+ACTOR_ABI_VERSION = 1
+_ACTOR_SYMBOLS = {
+    'astro_actor_abi_version': (ctypes.c_int, []),
+    'astro_actor_last_error': (ctypes.c_char_p, []),
+    'astro_explore': (ctypes.c_int, [ctypes.POINTER(AstroParams), ctypes.POINTER(AstroState),
+                                     ctypes.POINTER(AstroExplore), ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    'astro_episodes': (ctypes.c_int, [ctypes.POINTER(AstroEpisodes), ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p]),
+}
+
 _lib = None
 _qnet_lib = None
 _qtrain_lib = None
 _replay_lib = None
+_actor_lib = None
 
 
 class AstroError(RuntimeError):
@@ -358,4 +404,31 @@ def load_replay(path=REPLAY_LIB_PATH):
 def check_replay(rc, what):
     if rc != 0:
         msg = load_replay().astro_replay_last_error().decode(errors='replace')
+        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
+
+
+def load_actor(path=ACTOR_LIB_PATH):
+    """Load (once) and type libastro_actor.so.  Raises if it is absent or stale."""
+    global _actor_lib
+    if _actor_lib is not None:
+        return _actor_lib
+    if not os.path.exists(path):
+        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
+                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
+    import torch  # noqa: F401
+    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in _ACTOR_SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    v = lib.astro_actor_abi_version()
+    if v != ACTOR_ABI_VERSION:
+        raise AstroError('libastro_actor.so ABI %d != expected %d (rebuild)' % (v, ACTOR_ABI_VERSION))
+    _actor_lib = lib
+    return lib
+
+
+def check_actor(rc, what):
+    if rc != 0:
+        msg = load_actor().astro_actor_last_error().decode(errors='replace')
         raise AstroError('%s failed (%d): %s' % (what, rc, msg))

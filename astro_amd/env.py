@@ -520,37 +520,49 @@ class BatchedEnv:
         self._qvalues(net, q, None, None, 0.0)
         return q
 
-    def qcontrols(self, net, epsilon=0.0, seed=0, tick0=0, q_out=None):
+    def qcontrols(self, net, epsilon=0.0, seed=0, tick0=0, q_out=None, explore=None):
         """rl.QBot's decision for every ship (rl.py:195-209): int8 [N, S], the
         first maximal index of ``qvalues(net)`` -- or, with probability
         ``epsilon`` per ship and tick, the control ``controls('random', seed,
         tick0)`` draws (keyed by global ship id, so shards agree; epsilon = 1
         is exactly that policy).  q_out: a float32 [N, S, nout] tensor that
-        also receives the Q values."""
+        also receives the Q values.  explore: an ``actor.EpsilonGreedy`` of
+        this env -- the reference trainer's sticky exploration (rl.py:253-254)
+        instead of the coin: the greedy decision, then ``explore.apply(control,
+        draw=tick0)``; not together with ``epsilon``."""
+        if explore is not None and epsilon != 0.0:
+            raise ValueError('pass either epsilon or explore, not both')
         q = None if q_out is None else self._q_buffer(net, q_out)
         control = torch.empty((self.n_env, self.S), dtype=torch.int8, device=self.device)
-        explore = None
+        coin = None
         if epsilon != 0.0:
-            explore = _lib.AstroPolicy(kind=_lib.POLICIES['random'], seed=int(seed), tick0=int(tick0),
-                                       env_offset=self.env_offset)
-        self._qvalues(net, q, control, explore, epsilon)
+            coin = _lib.AstroPolicy(kind=_lib.POLICIES['random'], seed=int(seed), tick0=int(tick0),
+                                    env_offset=self.env_offset)
+        self._qvalues(net, q, control, coin, epsilon)
+        if explore is not None:
+            if explore.env is not self:
+                raise ValueError('explore belongs to another env')
+            explore.apply(control, tick0)
         return control
 
-    def rollout_q(self, net, ticks, epsilon=0.0, seed=0, tick0=0, opponent=None, auto_reset=None):
-        """``ticks`` steps driven by the network: each tick ``qcontrols(net,
-        epsilon, seed, tick0 + t)`` then ``step`` (a host loop of two launches
-        per tick).  opponent: None (the network plays every ship) or
-        'script' / 'nothing' / 'random': ship 1's controls come from
-        ``controls(opponent, seed, tick0 + t)``.  Returns (reward [ticks, N,
-        S], done [ticks, N], control [ticks, N, S])."""
-        ticks = int(ticks)
+    def _check_opponent(self, opponent):
         if opponent is not None and (self.S != 2 or opponent not in ('script', 'nothing', 'random')):
             raise ValueError("opponent needs a two-ship env and one of 'script', 'nothing', 'random'")
+
+    def rollout_q(self, net, ticks, epsilon=0.0, seed=0, tick0=0, opponent=None, auto_reset=None, explore=None):
+        """``ticks`` steps driven by the network: each tick ``qcontrols(net,
+        epsilon, seed, tick0 + t, explore=explore)`` then ``step`` (a host loop
+        of two launches per tick, three with ``explore``).  opponent: None (the
+        network plays every ship) or 'script' / 'nothing' / 'random': ship 1's
+        controls come from ``controls(opponent, seed, tick0 + t)``.  Returns
+        (reward [ticks, N, S], done [ticks, N], control [ticks, N, S])."""
+        ticks = int(ticks)
+        self._check_opponent(opponent)
         reward = torch.empty((ticks, self.n_env, self.S), dtype=torch.float32, device=self.device)
         done = torch.empty((ticks, self.n_env), dtype=torch.uint8, device=self.device)
         control = torch.empty((ticks, self.n_env, self.S), dtype=torch.int8, device=self.device)
         for t in range(ticks):
-            c = self.qcontrols(net, epsilon, seed, tick0 + t)
+            c = self.qcontrols(net, epsilon, seed, tick0 + t, explore=explore)
             if opponent is not None:
                 c[:, 1] = self.controls(opponent, seed, tick0 + t)[:, 1]
             control[t] = c
@@ -558,6 +570,41 @@ class BatchedEnv:
             reward[t] = r
             done[t] = d
         return reward, done, control
+
+    def play_q(self, net, opponent=None, games=1, explore=None, max_ticks=None, seed=0):
+        """``play`` with the network deciding: every env plays its next
+        ``games`` games (auto-reset onto its generate_configs stream) from its
+        current state, ``net`` greedy for every ship (rl.train's validation,
+        rl.py:352-355) or, with ``opponent`` ('script', 'nothing', 'random'),
+        for ship 0 against that bot as ship 1.  explore: an
+        ``actor.EpsilonGreedy`` applied to the network's decisions.  A host
+        loop of ``qcontrols``, ``step`` and ``actor.Episodes.push`` per tick;
+        the device count of finished games is read every 64 ticks only.
+        Returns ``play``'s (winner int64 [N, games], length int64 [N, games])."""
+        ep = self._play_q(net, opponent, games, explore, max_ticks, seed)
+        return ep.winner.to(torch.int64), ep.ticks.to(torch.int64)
+
+    def _play_q(self, net, opponent, games, explore, max_ticks, seed):
+        """play_q's loop; returns its ``actor.Episodes``."""
+        from . import actor
+        self._check_opponent(opponent)
+        G = int(games)
+        ep = actor.Episodes(self, G)
+        limit = max_ticks if max_ticks is not None else G * (self.schedule.timeout_tick + 1) + 64
+        t = 0
+        while True:
+            if t >= limit:
+                raise RuntimeError('play_q: games did not finish within %d ticks' % limit)
+            for _ in range(64):
+                c = self.qcontrols(net, tick0=t, explore=explore)
+                if opponent is not None:
+                    c[:, 1] = self.controls(opponent, seed, t)[:, 1]
+                _, r, d = self.step(c, auto_reset=True)
+                ep.push(r, d)
+                t += 1
+            if int(ep.got.min()) >= G:
+                break
+        return ep
 
     def stat_dict(self):
         v = self.stats.sum(0).cpu().tolist()

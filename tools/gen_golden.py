@@ -9,7 +9,8 @@ Test infrastructure only.  This script imports DouglasOrr/Astro's own
 ``core.create`` (core.py:86-135), ``core.generate_configs`` (core.py:77-83) and
 ``core.step`` (core.py:215-303), ``rl.ValueNetwork.get_features`` /
 ``to_batch`` (rl.py:36-112), ``rl.ValueNetwork.forward`` (rl.py:137-155) and
-``rl.QBotTrainer``'s experience bookkeeping (rl.py:249-258, 303-328),
+``rl.QBotTrainer``'s experience bookkeeping (rl.py:249-258, 303-328) and
+counts of ``rl.EpsilonGreedy``'s transitions (rl.py:10-29),
 as small ``.npz``/``.json`` fixtures.
 
 It refuses to run when ``/root/reference`` is absent, so it never runs on the
@@ -808,7 +809,54 @@ def gen_replay():
     print('wrote replay.npz', game_ticks, game_winner, [r.tolist() for r in game_reward])
 
 
+# ---------------------------------------------------------------------------
+# 14. rl.EpsilonGreedy (rl.py:10-29) as rl.QBotTrainer constructs it
+#     (rl.py:235-238): counts of its two-state process, no program text
+
+def gen_explore(seeds=8, ticks=200000, game=1500, dt=0.02):
+    """The reference's own EpsilonGreedy(t_in=1.0, t_out=0.1, seed) called once
+    per tick with state.t = tick * dt, the tick jumping back to 0 every ``game``
+    ticks (a new game).  Per seed: the calls made with no policy held and with
+    one held (t = 0 calls apart), the entries and exits among them, the
+    histogram of entered controls, and the transitions on t = 0 calls."""
+    rl = _import_rl()
+    State = types.SimpleNamespace
+    out = dict(out_ticks=[], entries=[], in_ticks=[], exits=[], hist=[], t0_ticks=[], t0_transitions=[])
+    for seed in range(seeds):
+        bot = rl.EpsilonGreedy(t_in=1.0, t_out=0.1, seed=seed)
+        c = dict(out_ticks=0, entries=0, in_ticks=0, exits=0, t0_ticks=0, t0_transitions=0)
+        hist = np.zeros(6, np.int64)
+        for k in range(ticks):
+            tick = k % game
+            before = bot._policy
+            after = bot(State(t=tick * dt))
+            moved = (before is None) != (after is None)
+            if tick == 0:
+                c['t0_ticks'] += 1
+                c['t0_transitions'] += int(moved)
+                continue
+            if before is None:
+                c['out_ticks'] += 1
+                if moved:
+                    c['entries'] += 1
+                    hist[int(after)] += 1
+            else:
+                assert after is None or after == before
+                c['in_ticks'] += 1
+                c['exits'] += int(moved)
+        for k, v in c.items():
+            out[k].append(v)
+        out['hist'].append(hist)
+    out = {k: np.array(v, np.int64) for k, v in out.items()}
+    np.savez_compressed(os.path.join(OUT, 'explore.npz'), seeds=np.int32(seeds), ticks=np.int64(ticks),
+                        game=np.int32(game), dt=np.float64(dt), t_in=np.float64(1.0), t_out=np.float64(0.1), **out)
+    print('wrote explore.npz', {k: v.sum(0).tolist() for k, v in out.items()})
+
+
 def generate():
+    if sys.argv[1:] == ['explore']:
+        gen_explore()
+        return
     if sys.argv[1:] == ['replay']:
         gen_replay()
         return
@@ -847,6 +895,7 @@ def generate():
     gen_config1()
     gen_long_games()
     gen_replay()
+    gen_explore()
 
 
 # No committed file may exceed 1 MiB: a larger fixture is stored as consecutive

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Train a Q-network with astro_amd.train.QTrainer on a fixed budget of ticks
+and record how it plays: every --every ticks the greedy network plays --games
+games per evaluation env as ship 0 against NothingBot and against ScriptBot
+(QTrainer.validate: env.play_q and Episodes.summary), as rl.train validates
+every `interval` games (rl.py:352-369).
+
+Training is self-play as in the reference: the network decides for both ships
+of every env, with the reference's sticky exploration (EpsilonGreedy(1.0, 0.1),
+one seed) and its learner constants (n_steps 100, discount 0.995, 1,024 samples
+per step, SGD with lr 1e-2).  The evaluation envs are re-created with the same
+seeds before every validation, so every point of the curve plays the same
+games.
+
+Writes one JSON document to --out: the arguments, and per validation the tick,
+the optimisation steps so far, the last loss per sample and both summaries.  No
+result is expected of it: it reports what the budget gave.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+
+from astro_amd import BatchedEnv, DEFAULT_CONFIG, ReplayBuffer, actor, qnet, train  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--n-env', type=int, default=4096)
+    ap.add_argument('--ticks', type=int, default=20000)
+    ap.add_argument('--every', type=int, default=2500)
+    ap.add_argument('--eval-envs', type=int, default=1024)
+    ap.add_argument('--games', type=int, default=1)
+    ap.add_argument('--max-time', type=float, default=20.0, help='max_time of the evaluation games, seconds')
+    ap.add_argument('--n-steps', type=int, default=100)
+    ap.add_argument('--ring', type=int, default=128)
+    ap.add_argument('--n-samples', type=int, default=1024)
+    ap.add_argument('--lr', type=float, default=1e-2)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--out', default=os.path.join('profiles', 'actor', 'learning_curve.json'))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'train_q needs a HIP device'
+    dev = 'cuda:0'
+    torch.manual_seed(args.seed)
+    env = BatchedEnv(DEFAULT_CONFIG, args.n_env, device=dev, b_cap=32)
+    env.reset()
+    net = qnet.QNetwork.from_module(qnet.ValueNetwork(solo=False), dev)
+    buf = ReplayBuffer(env.n_env, env.p_pad + env.b_cap, 2, args.ring, n_steps=args.n_steps, device=dev)
+    eg = actor.EpsilonGreedy(env, t_in=1.0, t_out=0.1, seed=args.seed)
+    tr = train.QTrainer(env, net, buf, eg, n_samples=args.n_samples, lr=args.lr, seed=args.seed)
+    eval_cfg = DEFAULT_CONFIG._replace(max_time=args.max_time)
+    curve = []
+    t0 = time.time()
+
+    def validate(tick):
+        point = dict(tick=tick, nstep=tr.nstep, seconds=round(time.time() - t0, 2),
+                     loss_per_sample=None if tr.last is None else float(tr.last['loss']) / int(tr.last['n']),
+                     finite=bool(torch.isfinite(net.weights).all()))
+        for opponent in ('nothing', 'script'):
+            ev = BatchedEnv(eval_cfg, args.eval_envs, device=dev, b_cap=32, env_offset=1 << 20)
+            ev.reset()
+            point[opponent] = tr.validate(ev, games=args.games, opponent=opponent)
+        curve.append(point)
+        print(json.dumps(point), flush=True)
+
+    validate(0)
+    for tick in range(args.every, args.ticks + 1, args.every):
+        tr.run(args.every)
+        validate(tick)
+    env.check_errors()
+    doc = dict(args=vars(args), device=torch.cuda.get_device_name(0), train_seconds=round(time.time() - t0, 2),
+               curve=curve)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(doc, f, indent=1)
+        f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
