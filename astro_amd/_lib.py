@@ -7,13 +7,14 @@ The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
 missing or its ABI version differs, every entry point raises.
 """
+import collections
 import ctypes
 import os
 
+# torch before any library is loaded: they bind to the HIP runtime already in the process
+import torch
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-# (ASTRO_LIB: another build of the same library, e.g. an A/B variant from tools/build_var.sh)
-LIB_PATH = os.environ.get('ASTRO_LIB') or os.path.join(HERE, 'libastro_hip.so')
-ABI_VERSION = 21
 
 STAT_NAMES = ('bullets_in', 'bullets_out', 'resets', 'collisions', 'timeouts',
               'overflows', 'planets', 'serial_resets')
@@ -171,8 +172,6 @@ class AstroQNet(ctypes.Structure):
 
 
 # libastro_qnet.so: a library of its own (libastro_hip.so and _SYMBOLS stay what they are)
-QNET_LIB_PATH = os.environ.get('ASTRO_QNET_LIB') or os.path.join(HERE, 'libastro_qnet.so')
-QNET_ABI_VERSION = 1
 QNET_HIDDEN = 32
 _QNET_SYMBOLS = {
     'astro_qnet_abi_version': (ctypes.c_int, []),
@@ -183,8 +182,6 @@ _QNET_SYMBOLS = {
 }
 
 # libastro_qtrain.so: the training half, again a library of its own (include/astro_qtrain.h)
-QTRAIN_LIB_PATH = os.environ.get('ASTRO_QTRAIN_LIB') or os.path.join(HERE, 'libastro_qtrain.so')
-QTRAIN_ABI_VERSION = 1
 _QTRAIN_SYMBOLS = {
     'astro_qtrain_abi_version': (ctypes.c_int, []),
     'astro_qtrain_last_error': (ctypes.c_char_p, []),
@@ -220,8 +217,6 @@ class AstroReplay(ctypes.Structure):
 
 
 # libastro_replay.so: the experience replay, a library of its own (include/astro_replay.h)
-REPLAY_LIB_PATH = os.environ.get('ASTRO_REPLAY_LIB') or os.path.join(HERE, 'libastro_replay.so')
-REPLAY_ABI_VERSION = 1
 _REPLAY_SYMBOLS = {
     'astro_replay_abi_version': (ctypes.c_int, []),
     'astro_replay_last_error': (ctypes.c_char_p, []),
@@ -271,8 +266,6 @@ class AstroEpisodes(ctypes.Structure):
 
 
 # libastro_actor.so: exploration and episode bookkeeping, a library of its own (include/astro_actor.h)
-ACTOR_LIB_PATH = os.environ.get('ASTRO_ACTOR_LIB') or os.path.join(HERE, 'libastro_actor.so')
-ACTOR_ABI_VERSION = 1
 _ACTOR_SYMBOLS = {
     'astro_actor_abi_version': (ctypes.c_int, []),
     'astro_actor_last_error': (ctypes.c_char_p, []),
@@ -282,153 +275,95 @@ _ACTOR_SYMBOLS = {
                                       ctypes.c_void_p]),
 }
 
-_lib = None
-_qnet_lib = None
-_qtrain_lib = None
-_replay_lib = None
-_actor_lib = None
-
 
 class AstroError(RuntimeError):
     pass
 
 
-def load(path=LIB_PATH):
-    """Load (once) and type the library.  Raises if it is absent or stale."""
-    global _lib
-    if _lib is not None:
-        return _lib
+# One row per library: what __graft_entry__.build() compiles (csrc/<source> ->
+# <file>) and what _load() checks.  env: the variable that names another build
+# of the library (ASTRO_LIB: e.g. an A/B variant from tools/build_var.sh);
+# handle: the module-level name that holds the loaded library.
+Lib = collections.namedtuple('Lib', 'key file source env abi version error symbols path handle')
+
+
+def _row(key, file, source, env, abi, prefix, symbols):
+    return Lib(key, file, source, env, abi, prefix + 'abi_version', prefix + 'last_error', symbols,
+               os.environ.get(env) or os.path.join(HERE, file), '_lib' if key == 'hip' else '_%s_lib' % key)
+
+
+LIBS = collections.OrderedDict((r.key, r) for r in (
+    _row('hip', 'libastro_hip.so', 'astro_kernels.hip', 'ASTRO_LIB', 21, 'astro_', _SYMBOLS),
+    _row('qnet', 'libastro_qnet.so', 'astro_qnet.hip', 'ASTRO_QNET_LIB', 1, 'astro_qnet_', _QNET_SYMBOLS),
+    _row('qtrain', 'libastro_qtrain.so', 'astro_qtrain.hip', 'ASTRO_QTRAIN_LIB', 1, 'astro_qtrain_', _QTRAIN_SYMBOLS),
+    _row('replay', 'libastro_replay.so', 'astro_replay.hip', 'ASTRO_REPLAY_LIB', 1, 'astro_replay_', _REPLAY_SYMBOLS),
+    _row('actor', 'libastro_actor.so', 'astro_actor.hip', 'ASTRO_ACTOR_LIB', 1, 'astro_actor_', _ACTOR_SYMBOLS),
+))
+LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
+QNET_LIB_PATH, QNET_ABI_VERSION = LIBS['qnet'].path, LIBS['qnet'].abi
+QTRAIN_LIB_PATH, QTRAIN_ABI_VERSION = LIBS['qtrain'].path, LIBS['qtrain'].abi
+REPLAY_LIB_PATH, REPLAY_ABI_VERSION = LIBS['replay'].path, LIBS['replay'].abi
+ACTOR_LIB_PATH, ACTOR_ABI_VERSION = LIBS['actor'].path, LIBS['actor'].abi
+
+# the loaded libraries (tools/ab.py sets _lib back to None to load another build)
+_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = None
+
+
+def _load(key, path):
+    """The library of LIBS[key], loaded from `path` and typed on the first call.  Raises if
+    it is absent or stale."""
+    L = LIBS[key]
+    lib = globals()[L.handle]
+    if lib is not None:
+        return lib
     if not os.path.exists(path):
         raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
                          'g.build()"` (hipcc --offload-arch=gfx950)' % path)
-    # torch first: the library binds to the HIP runtime already in the process
-    import torch  # noqa: F401
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    ab_any = os.environ.get('ASTRO_AB_ANY_ABI') == '1'
-    for name, (res, args) in _SYMBOLS.items():
-        if ab_any and not hasattr(lib, name):   # (an older A/B build: entry points it predates)
+    # (ASTRO_AB_ANY_ABI=1: tools/ab.py timing an older build of the main library, which
+    # lacks the entry points it predates and whose structs are a prefix of these -- never
+    # for results)
+    ab_any = key == 'hip' and os.environ.get('ASTRO_AB_ANY_ABI') == '1'
+    for name, (res, args) in L.symbols.items():
+        if ab_any and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    v = lib.astro_abi_version()
-    # (ASTRO_AB_ANY_ABI=1: tools/ab.py timing an older build whose structs are a
-    # prefix of these -- never for results)
-    if v != ABI_VERSION and not (os.environ.get('ASTRO_AB_ANY_ABI') == '1' and 12 <= v <= ABI_VERSION):
-        raise AstroError('libastro_hip.so ABI %d != expected %d (rebuild)' % (v, ABI_VERSION))
-    _lib = lib
+    v = getattr(lib, L.version)()
+    if v != L.abi and not (ab_any and 12 <= v <= L.abi):
+        raise AstroError('%s ABI %d != expected %d (rebuild)' % (L.file, v, L.abi))
+    globals()[L.handle] = lib
     return lib
 
 
-def check(rc, what):
-    if rc != 0:
-        msg = load().astro_last_error().decode(errors='replace')
-        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
+def _check(key, rc, what):
+    """Raise the library's last error for the entry point `what` that returned rc != 0."""
+    msg = getattr(_load(key, LIBS[key].path), LIBS[key].error)().decode(errors='replace')
+    raise AstroError('%s failed (%d): %s' % (what, rc, msg))
 
 
-def load_qnet(path=QNET_LIB_PATH):
-    """Load (once) and type libastro_qnet.so.  Raises if it is absent or stale."""
-    global _qnet_lib
-    if _qnet_lib is not None:
-        return _qnet_lib
-    if not os.path.exists(path):
-        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
-                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in _QNET_SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.astro_qnet_abi_version()
-    if v != QNET_ABI_VERSION:
-        raise AstroError('libastro_qnet.so ABI %d != expected %d (rebuild)' % (v, QNET_ABI_VERSION))
-    _qnet_lib = lib
-    return lib
+def _public(key):
+    """The library's public pair; what a call per step pays is one lookup and one compare."""
+    loaded, handle = globals(), LIBS[key].handle
+
+    def load(path=LIBS[key].path):
+        lib = loaded[handle]
+        return lib if lib is not None else _load(key, path)
+
+    def check(rc, what):
+        if rc != 0:
+            _check(key, rc, what)
+    return load, check
 
 
-def check_qnet(rc, what):
-    if rc != 0:
-        msg = load_qnet().astro_qnet_last_error().decode(errors='replace')
-        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
+load, check = _public('hip')
+load_qnet, check_qnet = _public('qnet')
+load_qtrain, check_qtrain = _public('qtrain')
+load_replay, check_replay = _public('replay')
+load_actor, check_actor = _public('actor')
 
 
-def load_qtrain(path=QTRAIN_LIB_PATH):
-    """Load (once) and type libastro_qtrain.so.  Raises if it is absent or stale."""
-    global _qtrain_lib
-    if _qtrain_lib is not None:
-        return _qtrain_lib
-    if not os.path.exists(path):
-        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
-                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in _QTRAIN_SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.astro_qtrain_abi_version()
-    if v != QTRAIN_ABI_VERSION:
-        raise AstroError('libastro_qtrain.so ABI %d != expected %d (rebuild)' % (v, QTRAIN_ABI_VERSION))
-    _qtrain_lib = lib
-    return lib
-
-
-def check_qtrain(rc, what):
-    if rc != 0:
-        msg = load_qtrain().astro_qtrain_last_error().decode(errors='replace')
-        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
-
-
-def load_replay(path=REPLAY_LIB_PATH):
-    """Load (once) and type libastro_replay.so.  Raises if it is absent or stale."""
-    global _replay_lib
-    if _replay_lib is not None:
-        return _replay_lib
-    if not os.path.exists(path):
-        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
-                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in _REPLAY_SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.astro_replay_abi_version()
-    if v != REPLAY_ABI_VERSION:
-        raise AstroError('libastro_replay.so ABI %d != expected %d (rebuild)' % (v, REPLAY_ABI_VERSION))
-    _replay_lib = lib
-    return lib
-
-
-def check_replay(rc, what):
-    if rc != 0:
-        msg = load_replay().astro_replay_last_error().decode(errors='replace')
-        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
-
-
-def load_actor(path=ACTOR_LIB_PATH):
-    """Load (once) and type libastro_actor.so.  Raises if it is absent or stale."""
-    global _actor_lib
-    if _actor_lib is not None:
-        return _actor_lib
-    if not os.path.exists(path):
-        raise AstroError('%s is missing: build it with `python -c "import __graft_entry__ as g; '
-                         'g.build()"` (hipcc --offload-arch=gfx950)' % path)
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in _ACTOR_SYMBOLS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.astro_actor_abi_version()
-    if v != ACTOR_ABI_VERSION:
-        raise AstroError('libastro_actor.so ABI %d != expected %d (rebuild)' % (v, ACTOR_ABI_VERSION))
-    _actor_lib = lib
-    return lib
-
-
-def check_actor(rc, what):
-    if rc != 0:
-        msg = load_actor().astro_actor_last_error().decode(errors='replace')
-        raise AstroError('%s failed (%d): %s' % (what, rc, msg))
+def stream_ptr(device):
+    """torch's current stream on `device` as the void * the entry points take."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

@@ -106,10 +106,6 @@ def episodes_host(h, reward, done):
 # ---------------------------------------------------------------------------
 # the device objects
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 class EpsilonGreedy:
     """rl.EpsilonGreedy for every ship of ``env`` (see the module).  ``policy``
     is the int8 [N, S] device tensor of held controls (-1: none): what
@@ -144,7 +140,7 @@ class EpsilonGreedy:
                              % (env.n_env, env.S, self.policy.device))
         _lib.check_actor(_lib.load_actor().astro_explore(
             ctypes.byref(env.params), ctypes.byref(env.state), ctypes.byref(self.c), int(draw), control.data_ptr(),
-            _stream(env.device)), 'astro_explore')
+            _lib.stream_ptr(env.device)), 'astro_explore')
         return control
 
 
@@ -198,7 +194,7 @@ class Episodes:
         if tuple(reward.shape) != (N, S) or tuple(done.shape) != (N,):
             raise ValueError('reward must be [%d, %d] and done [%d]' % (N, S, N))
         _lib.check_actor(_lib.load_actor().astro_episodes(
-            ctypes.byref(self.c), reward.data_ptr(), done.data_ptr(), _stream(self.device)), 'astro_episodes')
+            ctypes.byref(self.c), reward.data_ptr(), done.data_ptr(), _lib.stream_ptr(self.device)), 'astro_episodes')
         self._keep = (reward, done)   # alive until the call has run
 
     def summary(self):

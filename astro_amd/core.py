@@ -209,7 +209,7 @@ class _Shim:
             self.game_step_addr = ctypes.cast(self.game_step, ctypes.c_void_p).value
 
     def stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        return _lib.stream_ptr(self.env.device)
 
     def sync(self):
         """Results back to the host view; wait for them (busy-poll)."""

@@ -12,24 +12,12 @@
 //           (no game ended) store one int32.
 //
 // Both move well under 1 MB at 65,536 envs and are bound by the launch.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-
 #include "astro_actor.h"
+#include "astro_common.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr uint32_t TICK_MASK = (1u << 22) - 1;   // hdr[0]: tick (astro_step.h)
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 template <int S>
 __global__ __launch_bounds__(BLOCK) void explore_kernel(const int32_t *__restrict__ hdr, int8_t *__restrict__ policy,
@@ -42,11 +30,11 @@ __global__ __launch_bounds__(BLOCK) void explore_kernel(const int32_t *__restric
     int pol = policy[i];
     const uint32_t tick = uint32_t(hdr[4 * size_t(env)]) & TICK_MASK;
     if (tick != 0) {
-        const uint64_t g = (id0 + uint64_t(i)) * 0x9E3779B97F4A7C15ull + drawmix;
-        const uint64_t k = mix64(g) >> 11;
+        const uint64_t g = random_state(id0 + uint64_t(i), drawmix);
+        const uint64_t k = splitmix64(g) >> 11;
         if (pol < 0) {
             if (k >= stay_out) {
-                const uint64_t w = mix64(g + (1ull << 63));   // the word of id + 2^63 (the multiplier is odd)
+                const uint64_t w = splitmix64(g + (1ull << 63));   // the word of id + 2^63
                 pol = int(((w >> 32) * uint64_t(nrandom)) >> 32);
                 policy[i] = int8_t(pol);
             }
@@ -91,29 +79,6 @@ __global__ __launch_bounds__(BLOCK) void episodes_kernel(AstroEpisodes ep, const
     ep.length[e] = 0;
 }
 
-// ---------------------------------------------------------------------------
-// host side
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-bool aligned(const void *ptr, unsigned a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
-
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-1000 - int(e), "%s launch: %s", what, hipGetErrorString(e));
-    return 0;
-}
-
-unsigned blocks_for(int64_t n, int per) { return unsigned((n + per - 1) / per); }
-
 }  // namespace
 
 extern "C" {
@@ -137,15 +102,13 @@ int astro_explore(const AstroParams *p, const AstroState *s, const AstroExplore 
     if (!aligned(s->hdr, 16)) return fail(-109, "s.hdr must be 16-byte aligned");
     if (!control) return fail(-112, "control is NULL");
     const uint64_t id0 = uint64_t(ex->env_offset) * uint64_t(p->nships);
-    const uint64_t drawmix = (uint64_t(draw) + 1) * 0xD1B54A32D192ED03ull + ex->seed;
+    const uint64_t drawmix = draw_mix(uint64_t(draw), ex->seed);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(blocks_for(n, BLOCK)), block(BLOCK);
-    if (p->nships == 1)
-        hipLaunchKernelGGL(explore_kernel<1>, grid, block, 0, st, s->hdr, ex->policy, control, int(n), ex->stay_out,
+    with_nships(p->nships, [&](auto S) {
+        hipLaunchKernelGGL(explore_kernel<S()>, grid, block, 0, st, s->hdr, ex->policy, control, int(n), ex->stay_out,
                            ex->stay_in, id0, drawmix, uint32_t(ex->nrandom));
-    else
-        hipLaunchKernelGGL(explore_kernel<2>, grid, block, 0, st, s->hdr, ex->policy, control, int(n), ex->stay_out,
-                           ex->stay_in, id0, drawmix, uint32_t(ex->nrandom));
+    });
     return launched("astro_explore");
 }
 
@@ -165,10 +128,9 @@ int astro_episodes(const AstroEpisodes *ep, const float *reward, const uint8_t *
     if (!aligned(reward, 4)) return fail(-119, "reward must be 4-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(blocks_for(ep->n_env, BLOCK)), block(BLOCK);
-    if (ep->nships == 1)
-        hipLaunchKernelGGL(episodes_kernel<1>, grid, block, 0, st, *ep, reward, done);
-    else
-        hipLaunchKernelGGL(episodes_kernel<2>, grid, block, 0, st, *ep, reward, done);
+    with_nships(ep->nships, [&](auto S) {
+        hipLaunchKernelGGL(episodes_kernel<S()>, grid, block, 0, st, *ep, reward, done);
+    });
     return launched("astro_episodes");
 }
 

@@ -37,17 +37,11 @@
 // bit; with float32 state every stored value is the float32 rounding of the
 // reference's value computed from the same (float32) input state.
 
-#include <hip/hip_runtime.h>
-
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include <map>
 #include <mutex>
-#include <type_traits>
 #include <utility>
 
+#include "astro_common.h"
 #include "astro_step.h"
 
 namespace {
@@ -380,8 +374,7 @@ constexpr uint32_t MT_PROLOGUE = 397;
 // the reset path.  The words a step rewrites for a surviving
 // env are split: 0-1 (tick, counts) by the step wave, 2-3 (pending seed and
 // key) by whoever checks the pending seed -- the step wave, or its helper
-constexpr int TICK_BITS = 22;
-constexpr uint32_t TICK_MASK = (1u << TICK_BITS) - 1;
+// (TICK_MASK, the tick's 22 bits: astro_common.h)
 constexpr uint32_t KEY_VALID = 1u << 31;
 constexpr uint32_t UNDRAWN = 1u << 30;
 constexpr uint32_t SEED_MASK = (1u << 30) - 1;   // generate_configs seeds are randint(1 << 30)
@@ -872,10 +865,7 @@ __device__ __forceinline__ int tick_control(const TickDriver &d, int i, int s, s
     if (d.policy == ASTRO_POLICY_CONTROL) return int(d.control[(size_t(kt) * n_env + size_t(i)) * S + s]);
     if (ship_bot(d, s) == ASTRO_BOT_RANDOM) {
         const uint64_t id = uint64_t(d.env_offset + i) * uint64_t(S) + uint64_t(s);
-        uint64_t z = id * 0x9E3779B97F4A7C15ull + uint64_t(d.tick0 + kt + 1) * 0xD1B54A32D192ED03ull + d.seed;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
+        const uint64_t z = random_word(id, d.tick0 + kt, d.seed);
         return int(((z >> 32) * 6ull) >> 32);
     }
     return 2;   // script.NothingBot
@@ -893,42 +883,8 @@ __device__ __forceinline__ int tick_control(const TickDriver &d, int i, int s, s
 // Scalar ** 2 in the reference is pow(x, 2); x * x here (they differ only
 // where pow is not correctly rounded).
 
-// fmod(x, y) for finite x and y > 0 with |x / y| < 2^24 (float) / 2^53
-// (double), exactly, in five instructions instead of ocml's fmod: q =
-// trunc(x / y) is the true quotient's integer part or, when x / y rounded up
-// to the next integer, one more in magnitude (the division is correctly
-// rounded, so never one less); x - q y is then a multiple of y's last mantissa
-// bit smaller than y in magnitude -- exactly representable -- so the fma
-// returns it exactly, and the correction by +-y is an add whose exact result
-// (the true remainder) is representable too.  (tests/test_host.py checks the
-// argument with exact rationals.)
-template <typename C>
-__device__ __forceinline__ C exact_fmod(C x, C y) {
-    const C q = trunc(x / y);
-    C r = __builtin_fma(-q, y, x);
-    r = x >= C(0) ? (r < C(0) ? r + y : r) : (r > C(0) ? r - y : r);
-    return r;
-}
-__device__ __forceinline__ float exact_fmod(float x, float y) {
-    const float q = truncf(x / y);
-    float r = __builtin_fmaf(-q, y, x);
-    r = x >= 0.0f ? (r < 0.0f ? r + y : r) : (r > 0.0f ? r - y : r);
-    return r;
-}
-
-// util.norm_angle (util.py:125-132): ((b + pi) % (2 pi)) - pi with numpy's
-// floored remainder (npy_divmod: fmod, + divisor when the signs differ, +0
-// for a zero result), in C
-template <typename C>
-__device__ __forceinline__ C np_norm_angle(C b) {
-    const C pi = C(3.141592653589793);          // np.pi (float32: 3.1415927f)
-    const C two_pi = C(6.283185307179586);      // 2 * np.pi
-    const C x = b + pi;
-    // (|x| < 2^24 * 2 pi: bearings change by at most dt * ship_rspeed per tick)
-    C m = exact_fmod(x, two_pi);
-    m = m != C(0) ? (m < C(0) ? m + two_pi : m) : C(0);
-    return m - pi;
-}
+// (exact_fmod and np_norm_angle, util.norm_angle with numpy's floored
+// remainder: astro_common.h)
 
 __device__ __forceinline__ float np_atan2(float y, float x) { return atan2f(y, x); }
 __device__ __forceinline__ double np_atan2(double y, double x) { return atan2(y, x); }
@@ -1569,16 +1525,13 @@ constexpr int QW = ASTRO_QUAD_WAVES;
 constexpr int QBLOCK = 64 * QW;
 
 // A wave's own LDS traffic in order: every lane's writes before any lane's
-// later reads (LDS runs a wave's instructions in issue order; this keeps the
-// compiler from reordering around it).  No s_barrier: waves never wait for
-// each other.
+// later reads (wave_fence, astro_common.h).  No s_barrier: waves never wait
+// for each other.
 __device__ __forceinline__ void wave_sync() {
     if constexpr (QW == 1) {
         __syncthreads();
     } else {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        wave_fence();
     }
 }
 constexpr int QWIN = 1024;        // live bullets per window of the quad kernel's LDS index
@@ -3831,13 +3784,6 @@ __global__ __launch_bounds__(64 * RES_WPG, 2) void astro_rollout_res_kernel(Astr
 // for create()'s float32 ships (tick 0), float64 after; every value is then
 // stored as float32, as the reference's float32 feature array does.
 
-// ((b + pi) % (2 pi) - pi) / pi with numpy's floored remainder
-// (npy_divmod: fmod, + divisor when the signs differ, +0 for a zero result)
-template <typename C>
-__device__ __forceinline__ C norm_angle_over_pi(C b) {
-    return np_norm_angle<C>(b) / C(3.141592653589793);
-}
-
 // A block covers 256 consecutive (env, row) items: the per-env part (every
 // ship's five features, with norm_angle's exact fmod) is computed once per
 // env into LDS rather than once per row, and the block's 256 x D floats go out
@@ -3991,17 +3937,7 @@ __global__ __launch_bounds__(256) void astro_keytable_kernel(uint32_t *__restric
 // ---------------------------------------------------------------------------
 // host side
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-bool aligned16(const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+bool aligned16(const void *ptr) { return aligned(ptr, 16); }
 
 int check_state(const AstroState *s) {
     if (!s) return fail(-2, "state is NULL");
@@ -4066,12 +4002,6 @@ TickDriver driver_of(const AstroPolicy &q, int ticks) {
     d.bullet_speed = q.bullet_speed;
     d.ship_radius = q.ship_radius;
     return d;
-}
-
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-1000 - int(e), "%s launch failed: %s", what, hipGetErrorString(e));
-    return 0;
 }
 
 // kernel choice: the quad kernel fills the chip with 4 waves per SIMD where a

@@ -28,18 +28,13 @@
 // Numerics: float32 throughout (the MFMA is an exact f32 fma chain).  What
 // differs from the reference's float32 forward: the summation order,
 // softsign's divide (a multiply by v_rcp_f32, 1 ulp) and tanhf.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 
+#include "astro_common.h"
 #include "astro_qnet.h"
 
 namespace {
 
-constexpr uint32_t TICK_MASK = (1u << 22) - 1;   // hdr[0]: tick (astro_step.h)
 constexpr int NH = ASTRO_QNET_HIDDEN;
 constexpr int QN_WAVES = 4;
 constexpr int QN_BLOCK = 64 * QN_WAVES;
@@ -47,80 +42,18 @@ constexpr int SEGS = 32;          // (env, ego) segments per chunk = columns of 
 constexpr int LD = NH + 1;        // LDS row stride of a [32][32] float image (bank-conflict-free columns)
 constexpr int MAX_BLOCKS = 512;   // two workgroups per CU on 256 CUs
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 template <typename T> struct Store;
 template <> struct Store<float> { using V = float4; };
 template <> struct Store<double> { using V = double4; };
 
-// ---- restated from astro_kernels.hip (exact: built with -ffp-contract=off) ----
-
-// fmod(x, y) for finite x and y > 0 with |x / y| < 2^24 (float) / 2^53 (double), exactly
-template <typename C>
-__device__ __forceinline__ C exact_fmod(C x, C y) {
-    const C q = trunc(x / y);
-    C r = __builtin_fma(-q, y, x);
-    r = x >= C(0) ? (r < C(0) ? r + y : r) : (r > C(0) ? r - y : r);
-    return r;
-}
-__device__ __forceinline__ float exact_fmod(float x, float y) {
-    const float q = truncf(x / y);
-    float r = __builtin_fmaf(-q, y, x);
-    r = x >= 0.0f ? (r < 0.0f ? r + y : r) : (r > 0.0f ? r - y : r);
-    return r;
-}
-
-// util.norm_angle (util.py:125-132) with numpy's floored remainder
-template <typename C>
-__device__ __forceinline__ C np_norm_angle(C b) {
-    const C pi = C(3.141592653589793);
-    const C two_pi = C(6.283185307179586);
-    const C x = b + pi;
-    C m = exact_fmod(x, two_pi);
-    m = m != C(0) ? (m < C(0) ? m + two_pi : m) : C(0);
-    return m - pi;
-}
-template <typename C>
-__device__ __forceinline__ C norm_angle_over_pi(C b) {
-    return np_norm_angle<C>(b) / C(3.141592653589793);
-}
-
-// the splitmix64 word of ASTRO_POLICY_RANDOM (tick_control) for a global ship id and tick
-__device__ __forceinline__ uint64_t random_word(uint64_t id, int64_t tick, uint64_t seed) {
-    uint64_t z = id * 0x9E3779B97F4A7C15ull + uint64_t(tick + 1) * 0xD1B54A32D192ED03ull + seed;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-// A wave's own LDS traffic in order (LDS runs a wave's instructions in issue
-// order; this keeps the compiler from reordering around it).  No s_barrier:
-// the waves of a workgroup never wait for each other after the staging.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-}
-
 // a / (1 + |a|): the denominator is in [1, inf), so v_rcp_f32 (1 ulp) is safe
 __device__ __forceinline__ float softsign(float a) { return a * __builtin_amdgcn_rcpf(1.0f + fabsf(a)); }
-
-// output index held by accumulator register j of lane half h
-__device__ __forceinline__ constexpr int out_of(int j, int h) { return (j & 3) + 8 * (j >> 2) + 4 * h; }
 
 // acc += W x over the 32 inputs held as x's 16 registers (w: the lane's permuted weight columns)
 __device__ __forceinline__ f32x16 layer(const float (&w)[16], const f32x16 &x, f32x16 acc) {
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[j], x[j], acc, 0, 0, 0);
     return acc;
-}
-
-__device__ __forceinline__ f32x16 bias_of(const float *b, int h) {
-    f32x16 a;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) a[j] = b[out_of(j, h)];
-    return a;
 }
 
 struct Explore {
@@ -248,7 +181,7 @@ __global__ __launch_bounds__(QN_BLOCK, 2) void astro_qvalues_kernel(AstroParams 
             if (l < SEGS) W.segoff[l] = incl - rows;
             if (l == SEGS - 1) W.segoff[SEGS] = incl;
         }
-        wave_sync();
+        wave_fence();
         if (l < SEGS) {
             const int le = l / S, ego = l - le * S;
             float f[5 * S];
@@ -266,7 +199,7 @@ __global__ __launch_bounds__(QN_BLOCK, 2) void astro_qvalues_kernel(AstroParams 
                 W.ego[l][o] = a;
             }
         }
-        wave_sync();
+        wave_fence();
         const int total = __builtin_amdgcn_readfirstlane(W.segoff[SEGS]);
 
         // ---- phase B: the chunk's object rows, 32 per tile ----
@@ -321,7 +254,7 @@ __global__ __launch_bounds__(QN_BLOCK, 2) void astro_qvalues_kernel(AstroParams 
             acc = layer(wf1, x, bias_of(s_b[2], h));
 #pragma unroll
             for (int j = 0; j < 16; ++j) W.tile[c][out_of(j, h)] = acc[j];
-            wave_sync();
+            wave_fence();
             // max per segment: every lane walks the tile's 32 columns for
             // output c; a finished segment's maximum is stored, the last
             // one's carries into the next tile
@@ -339,10 +272,10 @@ __global__ __launch_bounds__(QN_BLOCK, 2) void astro_qvalues_kernel(AstroParams 
                     m = fmaxf(m, v[cc]);
                 }
             }
-            wave_sync();
+            wave_fence();
         }
         if (cur >= 0) W.pool[cur][c] = m;
-        wave_sync();
+        wave_fence();
 
         // ---- phase C: the head on the chunk's 32 pooled vectors (column c = segment c) ----
         {
@@ -390,24 +323,12 @@ __global__ __launch_bounds__(QN_BLOCK, 2) void astro_qvalues_kernel(AstroParams 
                 }
             }
         }
-        wave_sync();
+        wave_fence();
     }
 }
 
 // ---------------------------------------------------------------------------
 // host side
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-bool aligned(const void *ptr, unsigned a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
 
 template <typename T, int S>
 int launch(const AstroParams &p, const AstroState &s, const AstroQNet &net, float *q, int8_t *control,
@@ -417,9 +338,7 @@ int launch(const AstroParams &p, const AstroState &s, const AstroQNet &net, floa
     const int blocks = std::min((nchunks + QN_WAVES - 1) / QN_WAVES, MAX_BLOCKS);
     hipLaunchKernelGGL((astro_qvalues_kernel<T, S>), dim3(unsigned(blocks)), dim3(QN_BLOCK), 0, stream, p, s,
                        net.weights, int(net.nout), q, control, ex, nchunks);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-1000 - int(e), "astro_qvalues launch: %s", hipGetErrorString(e));
-    return 0;
+    return launched("astro_qvalues");
 }
 
 }  // namespace

@@ -39,13 +39,9 @@
 // differs from torch's float32: the summation order, softsign's divide (a
 // multiply by v_rcp_f32, 1 ulp; its derivative is that reciprocal squared)
 // and tanhf.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 
+#include "astro_common.h"
 #include "astro_qtrain.h"
 
 namespace {
@@ -65,28 +61,9 @@ constexpr int SCAN = 4;           // column-0 loads in flight per lane and scan 
 constexpr int RED_PARAMS = 16, RED_GROUPS = 16;   // the reduction's block: parameters x partial groups
 constexpr int RED_BLOCK = RED_PARAMS * RED_GROUPS;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// A wave's own LDS traffic in order (astro_qnet.hip)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-}
-
 // 1 / (1 + |a|): the denominator is in [1, inf), so v_rcp_f32 (1 ulp) is safe.
 // softsign(a) = a r, softsign'(a) = r r.
 __device__ __forceinline__ float ss_rcp(float a) { return __builtin_amdgcn_rcpf(1.0f + fabsf(a)); }
-
-// unit held by accumulator register j of lane half h
-__device__ __forceinline__ constexpr int out_of(int j, int h) { return (j & 3) + 8 * (j >> 2) + 4 * h; }
-
-__device__ __forceinline__ f32x16 bias_of(const float *b, int h) {
-    f32x16 a;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) a[j] = b[out_of(j, h)];
-    return a;
-}
 
 // acc + W x: w is a [32][LD] image of torch's [out][in] rows, x the 32 inputs in a lane's 16 registers
 __device__ __forceinline__ f32x16 layer_fwd(const float *w, const f32x16 &x, f32x16 acc, int c, int h) {
@@ -183,13 +160,13 @@ __device__ __forceinline__ int next_tile(WaveLds &W, Scan &sc, const float *fchu
         sc.pos += SCAN * 64;
         scan_fetch(sc, fchunk, limit, nf, l);
     }
-    wave_sync();
+    wave_fence();
     take = sc.cnt < 32 ? sc.cnt : 32;
     const int c = l & 31;
     const int slot = c < take ? W.ring[(sc.head + c) & (RING - 1)] : -1;
     sc.head = (sc.head + take) & (RING - 1);
     sc.cnt -= take;
-    wave_sync();
+    wave_fence();
     return slot;
 }
 
@@ -285,7 +262,7 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
             (&W.pool[0][0])[k] = 0.0f;
             (&W.arg[0][0])[k] = -1;
         }
-        wave_sync();
+        wave_fence();
 
         // ---- 1: forward over the live rows, max and argmax per (sample, unit) ----
         {
@@ -302,7 +279,7 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
                 store_rows(W, rows_next, l);
                 slot_next = next_tile<false>(W, sc, fchunk, limit, NF, rows, l, take);
                 rows_next = fetch_rows(fchunk, slot_next, NF, l);
-                wave_sync();
+                wave_fence();
                 f32x16 acc = f0_fwd();
                 f32x16 x;
 #pragma unroll
@@ -312,7 +289,7 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
                 for (int j = 0; j < 16; ++j) x[j] = acc[j] * ss_rcp(acc[j]);
                 acc = layer_fwd(s_w[1], x, bias_of(s_b[2], h), c, h);
                 put_tile(W.td, acc, c, h);
-                wave_sync();
+                wave_fence();
                 // every lane walks the tile's columns for unit c (both halves alike);
                 // a finished sample's result is stored, the last one's carries on
                 float v[32];
@@ -337,13 +314,13 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
                         }
                     }
                 }
-                wave_sync();
+                wave_fence();
             }
             if (cur >= 0) {
                 W.pool[cur][c] = m;
                 W.arg[cur][c] = ar;
             }
-            wave_sync();
+            wave_fence();
         }
 
         // ---- 2: the head on the chunk's 32 pooled vectors (column c = sample s0 + c) ----
@@ -409,30 +386,30 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
                 // v0
                 put_tile(W.ta, av1, c, h);
                 put_tile(W.td, d, c, h);
-                wave_sync();
+                wave_fence();
                 accum(dW[5], db[5], W.td, W.ta, c, h);
                 acc = layer_bwd(s_w[4], d, c, h);
 #pragma unroll
                 for (int j = 0; j < 16; ++j) d[j] = acc[j] * rv1[j] * rv1[j];
-                wave_sync();
+                wave_fence();
                 // v.1
                 put_tile(W.ta, av0, c, h);
                 put_tile(W.td, d, c, h);
-                wave_sync();
+                wave_fence();
                 accum(dW[4], db[4], W.td, W.ta, c, h);
                 acc = layer_bwd(s_w[3], d, c, h);
 #pragma unroll
                 for (int j = 0; j < 16; ++j) d[j] = acc[j] * rv0[j] * rv0[j];
-                wave_sync();
+                wave_fence();
                 // v.0: its input is the pooled image itself, [sample][unit]
                 put_tile(W.td, d, c, h);
-                wave_sync();
+                wave_fence();
                 accum(dW[3], db[3], W.td, W.pool, c, h);
                 acc = layer_bwd(s_w[2], d, c, h);
-                wave_sync();
+                wave_fence();
                 put_tile(W.pool, acc, c, h);   // the pooled units' gradients
             }
-            wave_sync();
+            wave_fence();
         }
 
         // ---- 3: backward over the live rows ----
@@ -449,7 +426,7 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
                 store_rows(W, rows_next, l);
                 slot_next = next_tile<ASTRO_QTRAIN_SPARSE != 0>(W, sc, fchunk, limit, NF, rows, l, take);
                 rows_next = fetch_rows(fchunk, slot_next, NF, l);
-                wave_sync();
+                wave_fence();
                 f32x16 acc = f0_fwd();
                 f32x16 r0, a0, r1, a1, d;
 #pragma unroll
@@ -471,24 +448,24 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
                 }
                 put_tile(W.ta, a1, c, h);
                 put_tile(W.td, d, c, h);
-                wave_sync();
+                wave_fence();
                 accum(dW[2], db[2], W.td, W.ta, c, h);
                 acc = layer_bwd(s_w[1], d, c, h);
 #pragma unroll
                 for (int j = 0; j < 16; ++j) d[j] = acc[j] * r1[j] * r1[j];
-                wave_sync();
+                wave_fence();
                 // f.0
                 put_tile(W.ta, a0, c, h);
                 put_tile(W.td, d, c, h);
-                wave_sync();
+                wave_fence();
                 accum(dW[1], db[1], W.td, W.ta, c, h);
                 acc = layer_bwd(s_w[0], d, c, h);
 #pragma unroll
                 for (int j = 0; j < 16; ++j) d[j] = acc[j] * r0[j] * r0[j];
-                wave_sync();
+                wave_fence();
                 // f0: its input is the feature image (lanes past its 16 columns add into unused columns)
                 put_tile(W.td, d, c, h);
-                wave_sync();
+                wave_fence();
 #pragma unroll
                 for (int kk = 0; kk < 16; ++kk) {
                     const float a = W.td[2 * kk + h][c];
@@ -496,7 +473,7 @@ __global__ __launch_bounds__(QT_BLOCK, 1) void astro_qtrain_kernel(
                     dW[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, dW[0], 0, 0, 0);
                     db[0] += a;
                 }
-                wave_sync();
+                wave_fence();
             }
         }
     }
@@ -552,18 +529,6 @@ __global__ __launch_bounds__(RED_BLOCK) void astro_qgrad_reduce_kernel(const flo
 // ---------------------------------------------------------------------------
 // host side
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-bool aligned(const void *ptr, unsigned a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
-
 int nparams_of(const AstroQNet &net) {
     const int nf = 5 + 5 * net.nships;
     return NH * nf + NH + 4 * (NH * NH + NH) + (NH + 1) * net.nout;
@@ -596,15 +561,11 @@ int launch(const AstroQNet &net, const float *features, int n, int rows, float *
     const int blocks = blocks_of(n);
     const float inv_n = 1.0f / float(n);
     const int np = nparams_of(net);
-    if (net.nships == 1)
-        hipLaunchKernelGGL((astro_qtrain_kernel<1, BWD>), dim3(unsigned(blocks)), dim3(QT_BLOCK), 0, stream, net.weights,
+    with_nships(net.nships, [&](auto S) {
+        hipLaunchKernelGGL((astro_qtrain_kernel<S(), BWD>), dim3(unsigned(blocks)), dim3(QT_BLOCK), 0, stream, net.weights,
                            int(net.nout), features, n, rows, q, qmax, action, target, inv_n, loss, partials, np, nchunks);
-    else
-        hipLaunchKernelGGL((astro_qtrain_kernel<2, BWD>), dim3(unsigned(blocks)), dim3(QT_BLOCK), 0, stream, net.weights,
-                           int(net.nout), features, n, rows, q, qmax, action, target, inv_n, loss, partials, np, nchunks);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-1000 - int(e), "%s launch: %s", what, hipGetErrorString(e));
-    return 0;
+    });
+    return launched(what);
 }
 
 }  // namespace
@@ -665,9 +626,7 @@ int astro_qgrad(const AstroQNet *net, const float *features, int32_t n, int32_t 
     }
     hipLaunchKernelGGL(astro_qgrad_reduce_kernel, dim3(unsigned((np + RED_PARAMS - 1) / RED_PARAMS)), dim3(RED_BLOCK), 0, st,
                        static_cast<const float *>(workspace), nparts, np, grad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-1000 - int(e), "astro_qgrad reduce launch: %s", hipGetErrorString(e));
-    return 0;
+    return launched("astro_qgrad reduce");
 }
 
 }  // extern "C"

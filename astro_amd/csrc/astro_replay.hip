@@ -30,14 +30,10 @@
 //          columns exchanged), of padding rows only column 0 is stored.
 //
 // update   a scatter of float32.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 
+#include "astro_common.h"
 #include "astro_replay.h"
 
 namespace {
@@ -79,12 +75,6 @@ Layout layout_of(int64_t m) {
     l.cls = align16(l.keys + size_t(m) * sizeof(uint32_t));
     l.total = align16(l.cls + size_t(m));
     return l;
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 // exclusive sum of x over the workgroup's SCAN_BLOCK threads in thread order; *total: the sum
@@ -179,7 +169,7 @@ __global__ __launch_bounds__(BLOCK) void replay_keys_kernel(const float *__restr
             const int nx = next[size_t(row) * N + env];
             if (nx != ASTRO_REPLAY_NEXT_PENDING && nx != head) {
                 const float l = loss[id];
-                const uint64_t z = mix64(uint64_t(id) * 0x9E3779B97F4A7C15ull + drawmix + seed);
+                const uint64_t z = random_word(uint64_t(id), drawmix + seed);
                 const double u = (double(z >> 11) + 0.5) * 0x1p-53;
                 const double E = -log(u);
                 if (l == INFINITY) {
@@ -432,18 +422,6 @@ __global__ __launch_bounds__(BLOCK) void replay_update_kernel(float *__restrict_
 // ---------------------------------------------------------------------------
 // host side
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-bool aligned(const void *ptr, unsigned a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
-
 int check_scalars(const AstroReplay *rb) {
     if (!rb) return fail(-100, "rb is NULL");
     if (rb->nships != 1 && rb->nships != 2) return fail(-101, "rb.nships must be 1 or 2, got %d", int(rb->nships));
@@ -462,14 +440,6 @@ int check_scalars(const AstroReplay *rb) {
 }
 
 int64_t ids_of(const AstroReplay &rb) { return int64_t(rb.ticks) * rb.n_env * rb.nships; }
-
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(-1000 - int(e), "%s launch: %s", what, hipGetErrorString(e));
-    return 0;
-}
-
-unsigned blocks_for(int64_t n, int per) { return unsigned((n + per - 1) / per); }
 
 }  // namespace
 
@@ -492,10 +462,9 @@ int astro_replay_push(const AstroReplay *rb, int64_t t, const int8_t *control, c
     if (!aligned(reward, 4)) return fail(-119, "reward must be 4-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(blocks_for(rb->n_env, BLOCK)), block(BLOCK);
-    if (rb->nships == 1)
-        hipLaunchKernelGGL(replay_push_kernel<1>, grid, block, 0, st, *rb, t, control, reward, done);
-    else
-        hipLaunchKernelGGL(replay_push_kernel<2>, grid, block, 0, st, *rb, t, control, reward, done);
+    with_nships(rb->nships, [&](auto S) {
+        hipLaunchKernelGGL(replay_push_kernel<S()>, grid, block, 0, st, *rb, t, control, reward, done);
+    });
     return launched("astro_replay_push");
 }
 
@@ -529,17 +498,15 @@ int astro_replay_sample(const AstroReplay *rb, int64_t t, int32_t n, uint64_t se
     uint32_t *keys = reinterpret_cast<uint32_t *>(ws + l.keys);
     uint8_t *cls = reinterpret_cast<uint8_t *>(ws + l.cls);
     const int written = int(t < rb->ticks ? t : rb->ticks), head = int(t % rb->ticks);
-    const uint64_t drawmix = (draw + 1) * 0xD1B54A32D192ED03ull;
+    const uint64_t drawmix = draw_mix(draw, 0);   // (the kernel adds the seed)
     const dim3 block(BLOCK), wide(std::min(blocks_for(m, BLOCK), unsigned(MAX_GRID)));
     const dim3 per_tile(blocks_for(l.ntiles, WAVES));
 
     hipLaunchKernelGGL(replay_init_kernel, dim3(blocks_for(3 * BINS, BLOCK)), block, 0, st, hist);
-    if (rb->nships == 1)
-        hipLaunchKernelGGL(replay_keys_kernel<1>, wide, block, 0, st, rb->loss, rb->next, int(rb->n_env), m, written, head,
+    with_nships(rb->nships, [&](auto S) {
+        hipLaunchKernelGGL(replay_keys_kernel<S()>, wide, block, 0, st, rb->loss, rb->next, int(rb->n_env), m, written, head,
                            seed, drawmix, keys, cls, hist);
-    else
-        hipLaunchKernelGGL(replay_keys_kernel<2>, wide, block, 0, st, rb->loss, rb->next, int(rb->n_env), m, written, head,
-                           seed, drawmix, keys, cls, hist);
+    });
     hipLaunchKernelGGL(replay_select_kernel<0>, dim3(1), dim3(SCAN_BLOCK), 0, st, sel, hist, int(n), count);
     hipLaunchKernelGGL(replay_hist_kernel<1>, wide, block, 0, st, sel, keys, cls, m, hist + BINS);
     hipLaunchKernelGGL(replay_select_kernel<1>, dim3(1), dim3(SCAN_BLOCK), 0, st, sel, hist + BINS, int(n), count);
@@ -568,12 +535,10 @@ int astro_replay_gather(const AstroReplay *rb, const int32_t *ids, int32_t n, fl
         return fail(-119, "ids, features, reward, discount and next_features must be 4-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(blocks_for(n, WAVES)), block(BLOCK);
-    if (rb->nships == 1)
-        hipLaunchKernelGGL(replay_gather_kernel<1>, grid, block, 0, st, *rb, ids, int(n), features, action, reward,
+    with_nships(rb->nships, [&](auto S) {
+        hipLaunchKernelGGL(replay_gather_kernel<S()>, grid, block, 0, st, *rb, ids, int(n), features, action, reward,
                            discount, next_features, terminal);
-    else
-        hipLaunchKernelGGL(replay_gather_kernel<2>, grid, block, 0, st, *rb, ids, int(n), features, action, reward,
-                           discount, next_features, terminal);
+    });
     return launched("astro_replay_gather");
 }
 

@@ -44,10 +44,6 @@ Observation = collections.namedtuple(
     'Observation', ('ships', 'ships_b', 'planets', 'nplanets', 'bullets', 'nbullets', 'tick'))
 
 
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 _KEY_TABLES = {}
 KEY_TABLE_SEEDS = 1 << 30
 
@@ -62,7 +58,7 @@ def key_table(device):
     if t is None:
         lib = _lib.load()
         t = torch.empty(KEY_TABLE_SEEDS, dtype=torch.int32, device=device)
-        _lib.check(lib.astro_keytable_build(t.data_ptr(), 0, KEY_TABLE_SEEDS, _stream_ptr(device)),
+        _lib.check(lib.astro_keytable_build(t.data_ptr(), 0, KEY_TABLE_SEEDS, _lib.stream_ptr(device)),
                    'astro_keytable_build')
         _KEY_TABLES[key] = t
     return t
@@ -189,7 +185,7 @@ class BatchedEnv:
         self.stream_seeds = _shard.stream_seeds(config, self.env_offset, N)
         seeds_t = torch.from_numpy(self.stream_seeds.view(np.int32)).to(dev)
         _lib.check(self.lib.astro_stream_init(ctypes.byref(self.state), seeds_t.data_ptr(),
-                                              _stream_ptr(dev)), 'astro_stream_init')
+                                              _lib.stream_ptr(dev)), 'astro_stream_init')
         torch.cuda.current_stream(dev).synchronize()
 
     # ------------------------------------------------------------------ calls
@@ -208,7 +204,7 @@ class BatchedEnv:
         _lib.check(self.lib.astro_reset(
             ctypes.byref(self.params), ctypes.byref(self.state),
             None if s is None else s.data_ptr(), None if m is None else m.data_ptr(),
-            _stream_ptr(self.device)), 'astro_reset')
+            _lib.stream_ptr(self.device)), 'astro_reset')
         self._keep = (m, s)   # keep the arguments alive until the call has run
         return self.obs()
 
@@ -254,7 +250,7 @@ class BatchedEnv:
         rc = self.lib.astro_step_many(
             ctypes.byref(self.params), ctypes.byref(self.state), control_ptr, int(k), reward_ptr, done_ptr,
             self.stats.data_ptr() if stats else None, 1 if ar else 0,
-            stream if stream is not None else _stream_ptr(self.device))
+            stream if stream is not None else _lib.stream_ptr(self.device))
         if rc != 0:
             _lib.check(rc, 'astro_step_many')
         self._last = False   # info(): the last tick's reward/done are not held here
@@ -266,7 +262,7 @@ class BatchedEnv:
             ctypes.byref(self.params), ctypes.byref(self.state), control_ptr,
             self.reward.data_ptr(), self.done.data_ptr(),
             self.stats.data_ptr() if stats else None, 1 if ar else 0,
-            stream if stream is not None else _stream_ptr(self.device))
+            stream if stream is not None else _lib.stream_ptr(self.device))
         if rc != 0:
             _lib.check(rc, 'astro_step')
         self._last = None   # info(): this launch's reward/done
@@ -393,7 +389,7 @@ class BatchedEnv:
         out = torch.empty((self.n_env, self.S), dtype=torch.int8, device=self.device)
         pol = self.policy(policy, seed, tick0, script_args)
         _lib.check(self.lib.astro_controls(ctypes.byref(self.params), ctypes.byref(self.state), ctypes.byref(pol),
-                                           out.data_ptr(), _stream_ptr(self.device)), 'astro_controls')
+                                           out.data_ptr(), _lib.stream_ptr(self.device)), 'astro_controls')
         return out
 
     def rollout(self, ticks, policy='random', seed=0, tick0=0, auto_reset=None, stats=True, script_args=None):
@@ -418,7 +414,7 @@ class BatchedEnv:
         _lib.check(self.lib.astro_rollout(
             ctypes.byref(self.params), ctypes.byref(self.state), ctypes.byref(pol), ticks,
             None if ctl is None else ctl.data_ptr(), reward.data_ptr(), done.data_ptr(),
-            self.stats.data_ptr() if stats else None, int(ar), _stream_ptr(self.device)), 'astro_rollout')
+            self.stats.data_ptr() if stats else None, int(ar), _lib.stream_ptr(self.device)), 'astro_rollout')
         self._keep_rollout = ctl
         self._last = (reward[-1], done[-1])   # info() describes the last tick
         return reward, done
@@ -486,7 +482,7 @@ class BatchedEnv:
             raise ValueError('out must be a contiguous float32 [%d, %d, %d] tensor on %s'
                              % (self.n_env, rows, D, self.device))
         _lib.check(self.lib.astro_features(ctypes.byref(self.params), ctypes.byref(self.state),
-                                           out.data_ptr(), rows, _stream_ptr(self.device)), 'astro_features')
+                                           out.data_ptr(), rows, _lib.stream_ptr(self.device)), 'astro_features')
         return out
 
     # ------------------------------------------------------- Q-network policy
@@ -499,7 +495,7 @@ class BatchedEnv:
             ctypes.byref(self.params), ctypes.byref(self.state), net.byref(),
             None if q is None else q.data_ptr(), None if control is None else control.data_ptr(),
             None if explore is None else ctypes.byref(explore), float(epsilon),
-            _stream_ptr(self.device)), 'astro_qvalues')
+            _lib.stream_ptr(self.device)), 'astro_qvalues')
 
     def _q_buffer(self, net, out):
         shape = (self.n_env, self.S, net.nout)

@@ -295,7 +295,7 @@ class QNetwork:
         if n == 0:      # (an empty tensor has no address)
             return
         lib = _lib.load_qtrain()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.weights.device).cuda_stream)
+        stream = _lib.stream_ptr(self.weights.device)
         _lib.check_qtrain(lib.astro_qforward(self.byref(), features.data_ptr(), n, rows,
                                              None if q is None else q.data_ptr(),
                                              None if qmax is None else qmax.data_ptr(), stream), 'astro_qforward')
@@ -352,7 +352,7 @@ class QNetwork:
         if ws is None or ws.numel() * 4 < need:
             ws = self._workspace = torch.empty(max(1, (need + 3) // 4), dtype=torch.float32,
                                                device=self.weights.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.weights.device).cuda_stream)
+        stream = _lib.stream_ptr(self.weights.device)
         _lib.check_qtrain(lib.astro_qgrad(self.byref(), features.data_ptr(), n, rows, action.data_ptr(),
                                           target.data_ptr(), loss.data_ptr(), grad.data_ptr(), ws.data_ptr(),
                                           ws.numel() * 4, stream), 'astro_qgrad')

@@ -190,9 +190,6 @@ class ReplayBuffer:
         self._count = torch.zeros(1, dtype=torch.int32, device=dev)
         self._workspace = None
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _arg(self, v, shape, dtype, what):
         if not torch.is_tensor(v) or v.device != self.device:
             v = torch.as_tensor(v, device=self.device)
@@ -230,7 +227,7 @@ class ReplayBuffer:
         r = self._arg(reward, (N, S), torch.float32, 'reward')
         d = self._arg(done, (N,), torch.uint8, 'done')
         _lib.check_replay(_lib.load_replay().astro_replay_push(
-            ctypes.byref(self.c), self.t, c.data_ptr(), r.data_ptr(), d.data_ptr(), self._stream()),
+            ctypes.byref(self.c), self.t, c.data_ptr(), r.data_ptr(), d.data_ptr(), _lib.stream_ptr(self.device)),
             'astro_replay_push')
         self._keep = (c, r, d)   # alive until the call has run
         self.t += 1
@@ -264,7 +261,7 @@ class ReplayBuffer:
     def _sample(self, n, seed, draw, ids, ws):
         _lib.check_replay(_lib.load_replay().astro_replay_sample(
             ctypes.byref(self.c), self.t, n, int(seed) & M64, int(draw) & M64, ids.data_ptr() if n else None,
-            self._count.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()),
+            self._count.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _lib.stream_ptr(self.device)),
             'astro_replay_sample')
         if n <= self.eligible_lower_bound():
             return ids
@@ -294,7 +291,7 @@ class ReplayBuffer:
         if n:
             _lib.check_replay(_lib.load_replay().astro_replay_gather(
                 ctypes.byref(self.c), ids.data_ptr(), n, f.data_ptr(), a.data_ptr(), r.data_ptr(), d.data_ptr(),
-                nf.data_ptr(), term.data_ptr(), self._stream()), 'astro_replay_gather')
+                nf.data_ptr(), term.data_ptr(), _lib.stream_ptr(self.device)), 'astro_replay_gather')
         return f, a, r, d, nf, term
 
     def update_loss(self, ids, loss):
@@ -304,5 +301,6 @@ class ReplayBuffer:
         loss = self._arg(loss, (n,), torch.float32, 'loss')
         if n:
             _lib.check_replay(_lib.load_replay().astro_replay_update(
-                ctypes.byref(self.c), ids.data_ptr(), loss.data_ptr(), n, self._stream()), 'astro_replay_update')
+                ctypes.byref(self.c), ids.data_ptr(), loss.data_ptr(), n, _lib.stream_ptr(self.device)),
+                'astro_replay_update')
             self._keep_loss = loss

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 OUT=${OUT:-/tmp/astro_isa.s}
 export FILTER=${FILTER:-step}
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
-  -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude --cuda-device-only -S "$@" \
+  -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -Iastro_amd/csrc --cuda-device-only -S "$@" \
   ${SRC:-astro_amd/csrc/astro_kernels.hip} -o $OUT 2>/dev/null || exit 1
 python3 - "$OUT" <<'PY'
 import os, re, sys
