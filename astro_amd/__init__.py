@@ -5,11 +5,13 @@ kernel (csrc/astro_kernels.hip, C-ABI include/astro_step.h); ``core``
 exposes the reference's single-game create/step/play surface on top of it;
 ``ReplayBuffer`` (replay.py) is the learner's experience replay on the device,
 ``EpsilonGreedy`` and ``Episodes`` (actor.py) its exploration and per-game
-bookkeeping, ``QTrainer`` (train.py) the training loop made of them.
+bookkeeping, ``QTrainer`` (train.py) the training loop made of them, ``SGD``,
+``RMSprop``, ``Adagrad`` and ``Adam`` (optim.py) its update rules.
 """
 from .config import (Bodies, Config, DEFAULT_CONFIG, Game, SOLO_CONFIG,  # noqa: F401
                      SOLO_EASY_CONFIG, State, Tick, generate_configs)
 from .env import BatchedEnv, Observation  # noqa: F401
 from .replay import ReplayBuffer  # noqa: F401
 from .actor import EpsilonGreedy, Episodes  # noqa: F401
+from .optim import SGD, Adagrad, Adam, RMSprop  # noqa: F401
 from .train import QTrainer  # noqa: F401

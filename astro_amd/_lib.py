@@ -1,7 +1,8 @@
 """ctypes binding of libastro_hip.so (include/astro_step.h), of
 libastro_qnet.so (include/astro_qnet.h), of libastro_qtrain.so
-(include/astro_qtrain.h), of libastro_replay.so (include/astro_replay.h) and of
-libastro_actor.so (include/astro_actor.h).
+(include/astro_qtrain.h), of libastro_replay.so (include/astro_replay.h), of
+libastro_actor.so (include/astro_actor.h) and of libastro_qopt.so
+(include/astro_qopt.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -276,6 +277,42 @@ _ACTOR_SYMBOLS = {
 }
 
 
+class AstroQOpt(ctypes.Structure):
+    """include/astro_qopt.h AstroQOpt: the hyperparameters of one optimiser step."""
+    _fields_ = [
+        ('kind', ctypes.c_int32),
+        ('nesterov', ctypes.c_int32),
+        ('lr', ctypes.c_float),
+        ('weight_decay', ctypes.c_float),
+        ('max_norm', ctypes.c_float),
+        ('momentum', ctypes.c_float),
+        ('alpha', ctypes.c_float),
+        ('one_minus_alpha', ctypes.c_float),
+        ('beta1', ctypes.c_float),
+        ('one_minus_beta1', ctypes.c_float),
+        ('beta2', ctypes.c_float),
+        ('one_minus_beta2', ctypes.c_float),
+        ('step_size', ctypes.c_float),
+        ('bc2', ctypes.c_float),
+        ('eps', ctypes.c_float),
+        ('tau', ctypes.c_float),
+    ]
+
+
+QOPT_KINDS = {'sgd': 0, 'rmsprop': 1, 'adagrad': 2, 'adam': 3}   # include/astro_qopt.h ASTRO_QOPT_*
+QOPT_MAX_PARAMS = 1 << 20
+QOPT_THREADS = 1024
+
+# libastro_qopt.so: the optimiser step, a library of its own (include/astro_qopt.h)
+_QOPT_SYMBOLS = {
+    'astro_qopt_abi_version': (ctypes.c_int, []),
+    'astro_qopt_last_error': (ctypes.c_char_p, []),
+    'astro_qopt_step': (ctypes.c_int, [ctypes.POINTER(AstroQOpt), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p]),
+}
+
+
 class AstroError(RuntimeError):
     pass
 
@@ -299,20 +336,29 @@ LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('replay', 'libastro_replay.so', 'astro_replay.hip', 'ASTRO_REPLAY_LIB', 1, 'astro_replay_', _REPLAY_SYMBOLS),
     _row('actor', 'libastro_actor.so', 'astro_actor.hip', 'ASTRO_ACTOR_LIB', 1, 'astro_actor_', _ACTOR_SYMBOLS),
 ))
+# Why two tables: LIBS is the five libraries whose symbol tables, ABI numbers
+# and very keys the host tests pin; a library that came after them is a row of
+# LATER_LIBS, made by the same _row and built, loaded and checked by the same
+# code, which looks its key up in ALL_LIBS (LIBS, then LATER_LIBS).
+LATER_LIBS = collections.OrderedDict((r.key, r) for r in (
+    _row('qopt', 'libastro_qopt.so', 'astro_qopt.hip', 'ASTRO_QOPT_LIB', 1, 'astro_qopt_', _QOPT_SYMBOLS),
+))
+ALL_LIBS = collections.OrderedDict(list(LIBS.items()) + list(LATER_LIBS.items()))
 LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
 QNET_LIB_PATH, QNET_ABI_VERSION = LIBS['qnet'].path, LIBS['qnet'].abi
 QTRAIN_LIB_PATH, QTRAIN_ABI_VERSION = LIBS['qtrain'].path, LIBS['qtrain'].abi
 REPLAY_LIB_PATH, REPLAY_ABI_VERSION = LIBS['replay'].path, LIBS['replay'].abi
 ACTOR_LIB_PATH, ACTOR_ABI_VERSION = LIBS['actor'].path, LIBS['actor'].abi
+QOPT_LIB_PATH, QOPT_ABI_VERSION = LATER_LIBS['qopt'].path, LATER_LIBS['qopt'].abi
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
-_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = None
+_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = _qopt_lib = None
 
 
 def _load(key, path):
-    """The library of LIBS[key], loaded from `path` and typed on the first call.  Raises if
+    """The library of ALL_LIBS[key], loaded from `path` and typed on the first call.  Raises if
     it is absent or stale."""
-    L = LIBS[key]
+    L = ALL_LIBS[key]
     lib = globals()[L.handle]
     if lib is not None:
         return lib
@@ -339,15 +385,15 @@ def _load(key, path):
 
 def _check(key, rc, what):
     """Raise the library's last error for the entry point `what` that returned rc != 0."""
-    msg = getattr(_load(key, LIBS[key].path), LIBS[key].error)().decode(errors='replace')
+    msg = getattr(_load(key, ALL_LIBS[key].path), ALL_LIBS[key].error)().decode(errors='replace')
     raise AstroError('%s failed (%d): %s' % (what, rc, msg))
 
 
 def _public(key):
     """The library's public pair; what a call per step pays is one lookup and one compare."""
-    loaded, handle = globals(), LIBS[key].handle
+    loaded, handle = globals(), ALL_LIBS[key].handle
 
-    def load(path=LIBS[key].path):
+    def load(path=ALL_LIBS[key].path):
         lib = loaded[handle]
         return lib if lib is not None else _load(key, path)
 
@@ -362,6 +408,7 @@ load_qnet, check_qnet = _public('qnet')
 load_qtrain, check_qtrain = _public('qtrain')
 load_replay, check_replay = _public('replay')
 load_actor, check_actor = _public('actor')
+load_qopt, check_qopt = _public('qopt')
 
 
 def stream_ptr(device):

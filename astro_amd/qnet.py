@@ -11,6 +11,8 @@ fused into one HIP kernel (csrc/astro_qnet.hip, include/astro_qnet.h).
 * ``QNetwork.forward`` / ``qmax`` / ``td_targets`` / ``grad`` / ``sgd_step``
   train the packed buffer in place on the device (csrc/astro_qtrain.hip,
   include/astro_qtrain.h): rl.QNetworkTrainer.step without a torch module.
+  ``step`` does the same with an ``astro_amd.optim`` rule, ``clone`` /
+  ``copy_from`` make a target network, ``td_targets(online=)`` Double-DQN targets.
 * ``forward64`` is the same forward pass in numpy float64 (the tests' truth),
   ``grad64`` its backward pass;
   ``QBot`` is the reference's evaluation bot for the single-game
@@ -315,14 +317,30 @@ class QNetwork:
         self._qforward(features, None, m)
         return m
 
-    def td_targets(self, reward, discount, next_features, terminal):
+    def td_targets(self, reward, discount, next_features, terminal, online=None):
         """rl.QBotTrainer._step's targets (rl.py:281-291): ``reward`` where
         ``terminal``, ``discount * max_a Q(next_features)`` elsewhere (a
         terminal sample's next_features may hold anything).  reward, terminal:
-        [n] tensors on the device; discount: a number or an [n] tensor."""
+        [n] tensors on the device; discount: a number or an [n] tensor.
+
+        online: another ``QNetwork`` of the same shape -- Double-DQN targets:
+        this network's value of the action the online network prefers,
+        ``discount * Q_self(next)[argmax_a Q_online(next)]``, the first maximal
+        output as ``np.argmax`` takes it (two ``forward`` calls and a few
+        elementwise launches on [n, nout] values)."""
         n, _ = self._features(next_features)
         reward = self._vector(reward, n, 'reward').to(torch.float32)
-        return _td_targets(reward, discount, self.qmax(next_features), self._vector(terminal, n, 'terminal'))
+        terminal = self._vector(terminal, n, 'terminal')
+        if online is None:
+            return _td_targets(reward, discount, self.qmax(next_features), terminal)
+        if (online.nships, online.nout) != (self.nships, self.nout):
+            raise ValueError('the online network has another shape')
+        qo = online.forward(next_features)
+        # np.argmax: the first index that attains the maximum, the first NaN if there is one
+        best = (qo == qo.max(1, keepdim=True).values) | qo.isnan()
+        index = torch.arange(self.nout, device=qo.device).expand_as(qo)
+        first = torch.where(best, index, self.nout - 1).min(1, keepdim=True).values
+        return _td_targets(reward, discount, self.forward(next_features).gather(1, first)[:, 0], terminal)
 
     def grad(self, features, action, target, loss_out=None, grad_out=None):
         """rl.QNetworkTrainer.step's loss and gradient (rl.py:184-188): y =
@@ -364,6 +382,35 @@ class QNetwork:
         loss, grad = self.grad(features, action, target)
         self.weights.add_(grad, alpha=-lr)
         return loss
+
+    def step(self, features, action, target, opt, target_net=None, tau=1.0):
+        """``grad`` then ``opt.apply(self, grad, target_net, tau)``: one
+        optimisation step with an ``astro_amd.optim`` rule on the packed buffer,
+        in place.  target_net: a ``clone()`` that follows the new weights
+        (``optim.Optimizer.apply``).  Returns the per-sample loss [n].
+        ``step`` with ``optim.SGD(lr)`` and ``sgd_step`` need not agree bit for
+        bit: torch's ``add_(alpha=)`` may fuse the multiply-add, the optimiser
+        kernel never does."""
+        loss, grad = self.grad(features, action, target)
+        opt.apply(self, grad, target_net, tau)
+        return loss
+
+    def clone(self):
+        """A new QNetwork with storage of its own and equal weights (a target
+        network), copied on the device."""
+        other = QNetwork.__new__(QNetwork)
+        other.nships, other.nout, other.device = self.nships, self.nout, self.device
+        other.weights = self.weights.clone()
+        other.c = _lib.AstroQNet(weights=other.weights.data_ptr(), nships=other.nships, nout=other.nout)
+        other._workspace = None
+        return other
+
+    def copy_from(self, other):
+        """Copy another QNetwork's weights in, on the device (no host trip)."""
+        if (other.nships, other.nout) != (self.nships, self.nout):
+            raise ValueError('the other network has another shape')
+        self.weights.copy_(other.weights)
+        return self
 
 
 class QBot:

@@ -8,6 +8,10 @@ One ``QTrainer.tick()`` is one tick of every env and, once the ring holds
 ``n_samples`` eligible experiences, ``n_ministeps`` optimisation steps -- the
 reference takes them when an n-step window closes, every ``n_steps`` ticks per
 bot; with thousands of envs a window closes somewhere on every tick.
+
+Options, all off by default: an ``astro_amd.optim`` update rule instead of
+``sgd_step``, a frozen target network for the targets, Double-DQN targets, and
+a scripted opponent as ship 1 (astro_qopt.h).
 """
 import torch
 
@@ -18,9 +22,21 @@ class QTrainer:
     """env: the training ``BatchedEnv``; net: a ``qnet.QNetwork``; buf: a
     ``ReplayBuffer`` of the env's shape; explore: an ``actor.EpsilonGreedy`` of
     the env (or None: greedy).  ``seed`` keys the replay sampling; the
-    exploration has its own."""
+    exploration has its own.
 
-    def __init__(self, env, net, buf, explore, n_samples=1024, n_ministeps=1, lr=1e-2, seed=0):
+    optimizer: an ``astro_amd.optim`` rule (``net.step`` instead of
+    ``net.sgd_step(..., lr=lr)``; ``lr`` is then the optimizer's own).
+    target_sync (needs an optimizer): the targets come from ``self.target``, a
+    frozen ``net.clone()`` -- an int K: hard-copied every K optimisation steps;
+    a float in (0, 1): Polyak-averaged with that tau on every step; both inside
+    the optimiser's launch.  double: Double-DQN targets (the action the online
+    network prefers, valued by the target network).  opponent: 'script',
+    'nothing' or 'random' -- ship 1 plays ``env.controls(opponent, seed, t)``
+    instead of the network's choice (its experiences still go to the ring:
+    Q-learning is off-policy; its exploration state still advances)."""
+
+    def __init__(self, env, net, buf, explore, n_samples=1024, n_ministeps=1, lr=1e-2, seed=0,
+                 optimizer=None, target_sync=None, double=False, opponent=None):
         if buf.n_env != env.n_env or buf.nships != env.S:
             raise ValueError('the replay buffer is [%d envs, %d ships], the env [%d, %d]'
                              % (buf.n_env, buf.nships, env.n_env, env.S))
@@ -28,6 +44,31 @@ class QTrainer:
         self.n_samples, self.n_ministeps, self.lr, self.seed = int(n_samples), int(n_ministeps), float(lr), int(seed)
         self.nstep = 0     # optimisation steps so far (rl.QNetworkTrainer.nstep)
         self.last = None
+        self.optimizer, self.double, self.opponent = optimizer, bool(double), opponent
+        self.target, self.sync_every, self.tau = None, None, 1.0
+        if target_sync is not None:
+            if optimizer is None:
+                raise ValueError('target_sync needs an optimizer (the target follows inside its launch)')
+            if isinstance(target_sync, int) and not isinstance(target_sync, bool) and target_sync >= 1:
+                self.sync_every = target_sync
+            elif isinstance(target_sync, float) and 0.0 < target_sync < 1.0:
+                self.tau = target_sync
+            else:
+                raise ValueError('target_sync must be an int >= 1 (steps between hard copies) or a float in (0, 1)')
+            self.target = net.clone()
+        env._check_opponent(opponent)
+
+    def _targets(self, r, d, nf, term):
+        valuer = self.net if self.target is None else self.target
+        return valuer.td_targets(r, d, nf, term, online=self.net) if self.double else valuer.td_targets(r, d, nf, term)
+
+    def _step(self, f, a, targets):
+        if self.optimizer is None:
+            return self.net.sgd_step(f, a, targets, lr=self.lr)
+        follow = self.target
+        if self.sync_every is not None and (self.nstep + 1) % self.sync_every != 0:
+            follow = None
+        return self.net.step(f, a, targets, self.optimizer, target_net=follow, tau=self.tau)
 
     def tick(self):
         """One tick of acting and (when the ring is ready) training.  Returns
@@ -39,6 +80,8 @@ class QTrainer:
         t = buf.t
         env.features(out=buf.head())
         control = env.qcontrols(net, tick0=t, explore=self.explore)
+        if self.opponent is not None:
+            control[:, 1] = env.controls(self.opponent, self.seed, t)[:, 1]
         _, reward, done = env.step(control)
         buf.push(control, reward, done)
         if buf.eligible_lower_bound() < self.n_samples:
@@ -47,7 +90,7 @@ class QTrainer:
         for m in range(self.n_ministeps):
             ids = buf.sample(self.n_samples, seed=self.seed, draw=t * self.n_ministeps + m)
             f, a, r, d, nf, term = buf.gather(ids)
-            loss = net.sgd_step(f, a, net.td_targets(r, d, nf, term), lr=self.lr)
+            loss = self._step(f, a, self._targets(r, d, nf, term))
             buf.update_loss(ids, loss)
             self.nstep += 1
             out = dict(loss=loss.sum(), n=torch.full((), ids.shape[0], dtype=torch.int32, device=loss.device))

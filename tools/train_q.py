@@ -10,7 +10,10 @@ of every env, with the reference's sticky exploration (EpsilonGreedy(1.0, 0.1),
 one seed) and its learner constants (n_steps 100, discount 0.995, 1,024 samples
 per step, SGD with lr 1e-2).  The evaluation envs are re-created with the same
 seeds before every validation, so every point of the curve plays the same
-games.
+games.  --optimizer, --target-sync, --double, --opponent, --max-norm and
+--weight-decay select QTrainer's options (astro_amd.optim); without them the
+run is the one described above.  The settings are part of the arguments the
+curve file records.
 
 Writes one JSON document to --out: the arguments, and per validation the tick,
 the optimisation steps so far, the last loss per sample and both summaries.  No
@@ -26,7 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
-from astro_amd import BatchedEnv, DEFAULT_CONFIG, ReplayBuffer, actor, qnet, train  # noqa: E402
+from astro_amd import BatchedEnv, DEFAULT_CONFIG, ReplayBuffer, actor, optim, qnet, train  # noqa: E402
 
 
 def main():
@@ -43,6 +46,16 @@ def main():
     ap.add_argument('--lr', type=float, default=1e-2)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--out', default=os.path.join('profiles', 'actor', 'learning_curve.json'))
+    ap.add_argument('--optimizer', choices=('sgd', 'momentum', 'rmsprop', 'adagrad', 'adam'), default='sgd',
+                    help='sgd with no other option: QNetwork.sgd_step, as before; otherwise an astro_amd.optim rule '
+                         '(momentum: SGD with momentum 0.9) at --lr')
+    ap.add_argument('--target-sync', default=None,
+                    help='an integer K: a target network hard-copied every K steps; a float in (0, 1): Polyak tau')
+    ap.add_argument('--double', action='store_true', help='Double-DQN targets')
+    ap.add_argument('--opponent', choices=('script', 'nothing', 'random'), default=None,
+                    help='ship 1 of the training envs plays this bot instead of the network')
+    ap.add_argument('--max-norm', type=float, default=None, help='clip the gradient norm to this')
+    ap.add_argument('--weight-decay', type=float, default=0.0)
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'train_q needs a HIP device'
     dev = 'cuda:0'
@@ -52,7 +65,17 @@ def main():
     net = qnet.QNetwork.from_module(qnet.ValueNetwork(solo=False), dev)
     buf = ReplayBuffer(env.n_env, env.p_pad + env.b_cap, 2, args.ring, n_steps=args.n_steps, device=dev)
     eg = actor.EpsilonGreedy(env, t_in=1.0, t_out=0.1, seed=args.seed)
-    tr = train.QTrainer(env, net, buf, eg, n_samples=args.n_samples, lr=args.lr, seed=args.seed)
+    sync = args.target_sync
+    if sync is not None:
+        sync = int(sync) if sync.lstrip('+').isdigit() else float(sync)
+    opt = None      # the defaults: sgd_step, today's run
+    if args.optimizer != 'sgd' or sync is not None or args.max_norm is not None or args.weight_decay:
+        common = dict(lr=args.lr, weight_decay=args.weight_decay, max_norm=args.max_norm)
+        opt = {'sgd': lambda: optim.SGD(**common), 'momentum': lambda: optim.SGD(momentum=0.9, **common),
+               'rmsprop': lambda: optim.RMSprop(**common), 'adagrad': lambda: optim.Adagrad(**common),
+               'adam': lambda: optim.Adam(**common)}[args.optimizer]()
+    tr = train.QTrainer(env, net, buf, eg, n_samples=args.n_samples, lr=args.lr, seed=args.seed, optimizer=opt,
+                        target_sync=sync, double=args.double, opponent=args.opponent)
     eval_cfg = DEFAULT_CONFIG._replace(max_time=args.max_time)
     curve = []
     t0 = time.time()
@@ -61,6 +84,8 @@ def main():
         point = dict(tick=tick, nstep=tr.nstep, seconds=round(time.time() - t0, 2),
                      loss_per_sample=None if tr.last is None else float(tr.last['loss']) / int(tr.last['n']),
                      finite=bool(torch.isfinite(net.weights).all()))
+        if opt is not None and opt.norm is not None:
+            point.update(grad_norm=float(opt.norm), skipped=int(opt.skipped))
         for opponent in ('nothing', 'script'):
             ev = BatchedEnv(eval_cfg, args.eval_envs, device=dev, b_cap=32, env_offset=1 << 20)
             ev.reset()
