@@ -6,7 +6,9 @@ exposes the reference's single-game create/step/play surface on top of it;
 ``ReplayBuffer`` (replay.py) is the learner's experience replay on the device,
 ``EpsilonGreedy`` and ``Episodes`` (actor.py) its exploration and per-game
 bookkeeping, ``QTrainer`` (train.py) the training loop made of them, ``SGD``,
-``RMSprop``, ``Adagrad`` and ``Adam`` (optim.py) its update rules.
+``RMSprop``, ``Adagrad`` and ``Adam`` (optim.py) its update rules, ``league``
+(league.py) the comparison of two networks: ``p_better``, ``find_better``,
+``compare``.
 """
 from .config import (Bodies, Config, DEFAULT_CONFIG, Game, SOLO_CONFIG,  # noqa: F401
                      SOLO_EASY_CONFIG, State, Tick, generate_configs)
@@ -15,3 +17,5 @@ from .replay import ReplayBuffer  # noqa: F401
 from .actor import EpsilonGreedy, Episodes  # noqa: F401
 from .optim import SGD, Adagrad, Adam, RMSprop  # noqa: F401
 from .train import QTrainer  # noqa: F401
+from . import league  # noqa: F401
+from .league import compare, find_better, p_better  # noqa: F401

@@ -1,8 +1,8 @@
 """ctypes binding of libastro_hip.so (include/astro_step.h), of
 libastro_qnet.so (include/astro_qnet.h), of libastro_qtrain.so
 (include/astro_qtrain.h), of libastro_replay.so (include/astro_replay.h), of
-libastro_actor.so (include/astro_actor.h) and of libastro_qopt.so
-(include/astro_qopt.h).
+libastro_actor.so (include/astro_actor.h), of libastro_qopt.so
+(include/astro_qopt.h) and of libastro_qduel.so (include/astro_qduel.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -313,6 +313,17 @@ _QOPT_SYMBOLS = {
 }
 
 
+# libastro_qduel.so: one Q-network per ship, a library of its own (include/astro_qduel.h)
+_QDUEL_SYMBOLS = {
+    'astro_qduel_abi_version': (ctypes.c_int, []),
+    'astro_qduel_last_error': (ctypes.c_char_p, []),
+    'astro_qvalues_ships': (ctypes.c_int, [ctypes.POINTER(AstroParams), ctypes.POINTER(AstroState),
+                                           ctypes.POINTER(ctypes.POINTER(AstroQNet)), ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(AstroPolicy), ctypes.c_double, ctypes.c_int32,
+                                           ctypes.c_void_p]),
+}
+
+
 class AstroError(RuntimeError):
     pass
 
@@ -339,26 +350,36 @@ LIBS = collections.OrderedDict((r.key, r) for r in (
 # Why two tables: LIBS is the five libraries whose symbol tables, ABI numbers
 # and very keys the host tests pin; a library that came after them is a row of
 # LATER_LIBS, made by the same _row and built, loaded and checked by the same
-# code, which looks its key up in ALL_LIBS (LIBS, then LATER_LIBS).
+# code.
 LATER_LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qopt', 'libastro_qopt.so', 'astro_qopt.hip', 'ASTRO_QOPT_LIB', 1, 'astro_qopt_', _QOPT_SYMBOLS),
 ))
 ALL_LIBS = collections.OrderedDict(list(LIBS.items()) + list(LATER_LIBS.items()))
+# The third table is the open-ended one: the host tests pin LATER_LIBS and
+# ALL_LIBS to what they were when they were written as well, so every library
+# from here on is a row of OPEN_LIBS, and no test may pin ITS key set.
+# EVERY_LIB (LIBS, LATER_LIBS, OPEN_LIBS) is what the code below and
+# __graft_entry__ look a key up in.
+OPEN_LIBS = collections.OrderedDict((r.key, r) for r in (
+    _row('qduel', 'libastro_qduel.so', 'astro_qduel.hip', 'ASTRO_QDUEL_LIB', 1, 'astro_qduel_', _QDUEL_SYMBOLS),
+))
+EVERY_LIB = collections.OrderedDict(list(ALL_LIBS.items()) + list(OPEN_LIBS.items()))
 LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
 QNET_LIB_PATH, QNET_ABI_VERSION = LIBS['qnet'].path, LIBS['qnet'].abi
 QTRAIN_LIB_PATH, QTRAIN_ABI_VERSION = LIBS['qtrain'].path, LIBS['qtrain'].abi
 REPLAY_LIB_PATH, REPLAY_ABI_VERSION = LIBS['replay'].path, LIBS['replay'].abi
 ACTOR_LIB_PATH, ACTOR_ABI_VERSION = LIBS['actor'].path, LIBS['actor'].abi
 QOPT_LIB_PATH, QOPT_ABI_VERSION = LATER_LIBS['qopt'].path, LATER_LIBS['qopt'].abi
+QDUEL_LIB_PATH, QDUEL_ABI_VERSION = OPEN_LIBS['qduel'].path, OPEN_LIBS['qduel'].abi
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
-_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = _qopt_lib = None
+_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = _qopt_lib = _qduel_lib = None
 
 
 def _load(key, path):
-    """The library of ALL_LIBS[key], loaded from `path` and typed on the first call.  Raises if
+    """The library of EVERY_LIB[key], loaded from `path` and typed on the first call.  Raises if
     it is absent or stale."""
-    L = ALL_LIBS[key]
+    L = EVERY_LIB[key]
     lib = globals()[L.handle]
     if lib is not None:
         return lib
@@ -385,15 +406,15 @@ def _load(key, path):
 
 def _check(key, rc, what):
     """Raise the library's last error for the entry point `what` that returned rc != 0."""
-    msg = getattr(_load(key, ALL_LIBS[key].path), ALL_LIBS[key].error)().decode(errors='replace')
+    msg = getattr(_load(key, EVERY_LIB[key].path), EVERY_LIB[key].error)().decode(errors='replace')
     raise AstroError('%s failed (%d): %s' % (what, rc, msg))
 
 
 def _public(key):
     """The library's public pair; what a call per step pays is one lookup and one compare."""
-    loaded, handle = globals(), ALL_LIBS[key].handle
+    loaded, handle = globals(), EVERY_LIB[key].handle
 
-    def load(path=ALL_LIBS[key].path):
+    def load(path=EVERY_LIB[key].path):
         lib = loaded[handle]
         return lib if lib is not None else _load(key, path)
 
@@ -409,6 +430,7 @@ load_qtrain, check_qtrain = _public('qtrain')
 load_replay, check_replay = _public('replay')
 load_actor, check_actor = _public('actor')
 load_qopt, check_qopt = _public('qopt')
+load_qduel, check_qduel = _public('qduel')
 
 
 def stream_ptr(device):

@@ -99,6 +99,10 @@ def _dev_tensor(lib, shape, dtype, device, kind):
     return t
 
 
+class _PerShip(tuple):
+    """The per-ship form of a Q-network argument after ``BatchedEnv._per_ship`` checked it."""
+
+
 class BatchedEnv:
     """N lockstep games of one Config on one device.
 
@@ -487,7 +491,47 @@ class BatchedEnv:
 
     # ------------------------------------------------------- Q-network policy
 
+    def _per_ship(self, net):
+        """None for one ``QNetwork``; for the per-ship form (a sequence of S
+        entries, each a ``QNetwork`` or None) its checked tuple."""
+        if type(net) is _PerShip:      # checked already (a trainer's, a loop's: once, not per tick)
+            return net
+        if not isinstance(net, (list, tuple)):
+            return None
+        from .qnet import QNetwork
+        nets = _PerShip(net)
+        if len(nets) != self.S:
+            raise ValueError('the per-ship form takes %d entries (one per ship), got %d' % (self.S, len(nets)))
+        if any(n is not None and not isinstance(n, QNetwork) for n in nets):
+            raise ValueError('every entry of the per-ship form is a QNetwork or None')
+        have = [n for n in nets if n is not None]
+        if not have:
+            raise ValueError('the per-ship form needs at least one network')
+        for n in have:
+            if n.weights.device != self.hdr.device:
+                raise ValueError('the network is on %s, the env on %s' % (n.weights.device, self.hdr.device))
+            if n.nships != self.S:
+                raise ValueError('a network for %d ships in an env of %d' % (n.nships, self.S))
+            if n.nout != have[0].nout:
+                raise ValueError('the networks differ in nout (%d and %d)' % (have[0].nout, n.nout))
+        return nets
+
+    def _qvalues_ships(self, nets, q, control, explore, epsilon, max_blocks=0):
+        """astro_qvalues_ships (include/astro_qduel.h) on ``_per_ship``'s tuple."""
+        arr = (ctypes.POINTER(_lib.AstroQNet) * 2)()
+        for k, n in enumerate(nets):
+            if n is not None:
+                arr[k] = ctypes.pointer(n.c)
+        _lib.check_qduel(_lib.load_qduel().astro_qvalues_ships(
+            ctypes.byref(self.params), ctypes.byref(self.state), arr,
+            None if q is None else q.data_ptr(), None if control is None else control.data_ptr(),
+            None if explore is None else ctypes.byref(explore), float(epsilon), int(max_blocks),
+            _lib.stream_ptr(self.device)), 'astro_qvalues_ships')
+
     def _qvalues(self, net, q, control, explore, epsilon):
+        nets = self._per_ship(net)
+        if nets is not None:
+            return self._qvalues_ships(nets, q, control, explore, epsilon)
         if net.weights.device != self.hdr.device:
             raise ValueError('the network is on %s, the env on %s' % (net.weights.device, self.hdr.device))
         qlib = _lib.load_qnet()
@@ -498,7 +542,9 @@ class BatchedEnv:
             _lib.stream_ptr(self.device)), 'astro_qvalues')
 
     def _q_buffer(self, net, out):
-        shape = (self.n_env, self.S, net.nout)
+        nets = self._per_ship(net)
+        nout = net.nout if nets is None else [n for n in nets if n is not None][0].nout
+        shape = (self.n_env, self.S, nout)
         if out is None:
             return torch.empty(shape, dtype=torch.float32, device=self.device)
         if (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
@@ -511,7 +557,16 @@ class BatchedEnv:
         every env's current state: float32 [N, S, nout], computed by one
         kernel straight from the state arrays (astro_qvalues; ``net`` is an
         astro_amd.qnet.QNetwork).  The values are those of the network on
-        ``features()`` and its column-swapped copy, to float32 rounding."""
+        ``features()`` and its column-swapped copy, to float32 rounding.
+
+        The per-ship form: ``net`` is a sequence of S entries, each a
+        ``QNetwork`` or None -- ship s is evaluated with ``net[s]``, bit for
+        bit what ``qvalues(net[s])`` gives for that ship, in one kernel
+        (astro_qvalues_ships, include/astro_qduel.h).  A None ship is not
+        evaluated: its rows of ``out`` keep what they held (of a fresh buffer
+        they are unspecified).  ValueError unless there are S entries, at
+        least one network, all on the env's device, for S ships and with
+        equal nout."""
         q = self._q_buffer(net, out)
         self._qvalues(net, q, None, None, 0.0)
         return q
@@ -525,9 +580,16 @@ class BatchedEnv:
         also receives the Q values.  explore: an ``actor.EpsilonGreedy`` of
         this env -- the reference trainer's sticky exploration (rl.py:253-254)
         instead of the coin: the greedy decision, then ``explore.apply(control,
-        draw=tick0)``; not together with ``epsilon``."""
+        draw=tick0)``; not together with ``epsilon``.
+
+        ``net`` may be the per-ship form of ``qvalues``.  ``epsilon`` /
+        ``explore`` apply to every ship.  A None ship's rows of ``q_out`` keep
+        what they held, and its column of the returned controls is
+        unspecified (the tensor comes from ``torch.empty``; ``explore`` may
+        still write a held control there): fill it before stepping."""
         if explore is not None and epsilon != 0.0:
             raise ValueError('pass either epsilon or explore, not both')
+        net = self._per_ship(net) or net
         q = None if q_out is None else self._q_buffer(net, q_out)
         control = torch.empty((self.n_env, self.S), dtype=torch.int8, device=self.device)
         coin = None
@@ -542,25 +604,53 @@ class BatchedEnv:
         return control
 
     def _check_opponent(self, opponent):
-        if opponent is not None and (self.S != 2 or opponent not in ('script', 'nothing', 'random')):
-            raise ValueError("opponent needs a two-ship env and one of 'script', 'nothing', 'random'")
+        from .qnet import QNetwork
+        if opponent is None:
+            return
+        named = isinstance(opponent, str) and opponent in ('script', 'nothing', 'random')
+        if self.S != 2 or not (named or isinstance(opponent, QNetwork)):
+            raise ValueError("opponent needs a two-ship env and one of 'script', 'nothing', 'random' or a QNetwork")
+
+    def _with_opponent(self, net, opponent):
+        """(what ``qcontrols`` takes, the scripted name whose controls fill
+        ship 1's column or None): ``net`` alone without an opponent, ``(net,
+        opponent)`` against a network, ``(net, None)`` against a bot -- ship
+        1's Q values, which the bot's controls would overwrite, are not
+        computed."""
+        self._check_opponent(opponent)
+        if opponent is None:
+            nets = self._per_ship(net)
+            return (net if nets is None else nets), None
+        if isinstance(net, (list, tuple)):
+            raise ValueError('opponent goes with one QNetwork, not with the per-ship form')
+        if isinstance(opponent, str):
+            return self._per_ship((net, None)), opponent
+        return self._per_ship((net, opponent)), None
 
     def rollout_q(self, net, ticks, epsilon=0.0, seed=0, tick0=0, opponent=None, auto_reset=None, explore=None):
         """``ticks`` steps driven by the network: each tick ``qcontrols(net,
         epsilon, seed, tick0 + t, explore=explore)`` then ``step`` (a host loop
-        of two launches per tick, three with ``explore``).  opponent: None (the
-        network plays every ship) or 'script' / 'nothing' / 'random': ship 1's
-        controls come from ``controls(opponent, seed, tick0 + t)``.  Returns
-        (reward [ticks, N, S], done [ticks, N], control [ticks, N, S])."""
+        of two launches per tick, three with ``explore``).  ``net``: a
+        ``QNetwork`` or ``qvalues``' per-ship form (every ship needs a network
+        then).  opponent: None (``net`` plays every ship), 'script' / 'nothing'
+        / 'random': ship 1's controls come from ``controls(opponent, seed,
+        tick0 + t)`` and only ship 0 is evaluated, or a ``QNetwork``: ship 1
+        plays it, the call runs as ``(net, opponent)``.  ``epsilon`` /
+        ``explore`` apply to every ship a network plays -- with a network
+        opponent that is both ships; a scripted opponent's controls replace
+        whatever exploration chose for ship 1.  Returns (reward [ticks, N, S],
+        done [ticks, N], control [ticks, N, S])."""
         ticks = int(ticks)
-        self._check_opponent(opponent)
+        net, bot = self._with_opponent(net, opponent)
+        if bot is None and isinstance(net, (list, tuple)) and None in net:
+            raise ValueError('every ship needs a network (or name a scripted opponent)')
         reward = torch.empty((ticks, self.n_env, self.S), dtype=torch.float32, device=self.device)
         done = torch.empty((ticks, self.n_env), dtype=torch.uint8, device=self.device)
         control = torch.empty((ticks, self.n_env, self.S), dtype=torch.int8, device=self.device)
         for t in range(ticks):
             c = self.qcontrols(net, epsilon, seed, tick0 + t, explore=explore)
-            if opponent is not None:
-                c[:, 1] = self.controls(opponent, seed, tick0 + t)[:, 1]
+            if bot is not None:
+                c[:, 1] = self.controls(bot, seed, tick0 + t)[:, 1]
             control[t] = c
             _, r, d = self.step(control[t], auto_reset=auto_reset)
             reward[t] = r
@@ -572,8 +662,11 @@ class BatchedEnv:
         ``games`` games (auto-reset onto its generate_configs stream) from its
         current state, ``net`` greedy for every ship (rl.train's validation,
         rl.py:352-355) or, with ``opponent`` ('script', 'nothing', 'random'),
-        for ship 0 against that bot as ship 1.  explore: an
-        ``actor.EpsilonGreedy`` applied to the network's decisions.  A host
+        for ship 0 against that bot as ship 1, or with a ``QNetwork`` as
+        ``opponent`` against that network as ship 1 (``net`` may also be
+        ``qvalues``' per-ship form with a network for every ship).  explore: an
+        ``actor.EpsilonGreedy`` applied to the networks' decisions (both
+        ships' with a network opponent).  A host
         loop of ``qcontrols``, ``step`` and ``actor.Episodes.push`` per tick;
         the device count of finished games is read every 64 ticks only.
         Returns ``play``'s (winner int64 [N, games], length int64 [N, games])."""
@@ -583,7 +676,9 @@ class BatchedEnv:
     def _play_q(self, net, opponent, games, explore, max_ticks, seed):
         """play_q's loop; returns its ``actor.Episodes``."""
         from . import actor
-        self._check_opponent(opponent)
+        net, bot = self._with_opponent(net, opponent)
+        if bot is None and isinstance(net, (list, tuple)) and None in net:
+            raise ValueError('every ship needs a network (or name a scripted opponent)')
         G = int(games)
         ep = actor.Episodes(self, G)
         limit = max_ticks if max_ticks is not None else G * (self.schedule.timeout_tick + 1) + 64
@@ -593,8 +688,8 @@ class BatchedEnv:
                 raise RuntimeError('play_q: games did not finish within %d ticks' % limit)
             for _ in range(64):
                 c = self.qcontrols(net, tick0=t, explore=explore)
-                if opponent is not None:
-                    c[:, 1] = self.controls(opponent, seed, t)[:, 1]
+                if bot is not None:
+                    c[:, 1] = self.controls(bot, seed, t)[:, 1]
                 _, r, d = self.step(c, auto_reset=True)
                 ep.push(r, d)
                 t += 1

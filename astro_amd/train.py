@@ -10,8 +10,9 @@ reference takes them when an n-step window closes, every ``n_steps`` ticks per
 bot; with thousands of envs a window closes somewhere on every tick.
 
 Options, all off by default: an ``astro_amd.optim`` update rule instead of
-``sgd_step``, a frozen target network for the targets, Double-DQN targets, and
-a scripted opponent as ship 1 (astro_qopt.h).
+``sgd_step``, a frozen target network for the targets, Double-DQN targets
+(astro_qopt.h), and an opponent as ship 1: a scripted bot, a fixed network or a
+snapshot of the learner refreshed every K steps (astro_qduel.h).
 """
 import torch
 
@@ -33,10 +34,18 @@ class QTrainer:
     network prefers, valued by the target network).  opponent: 'script',
     'nothing' or 'random' -- ship 1 plays ``env.controls(opponent, seed, t)``
     instead of the network's choice (its experiences still go to the ring:
-    Q-learning is off-policy; its exploration state still advances)."""
+    Q-learning is off-policy; its exploration state still advances), and ship
+    1's Q values are not computed at all.  opponent=<QNetwork>: ship 1 plays
+    that fixed network, ``self.rival``, in the same launch that evaluates
+    ``net`` for ship 0.  opponent='snapshot' with opponent_sync=K (an int >= 1;
+    required with 'snapshot', rejected otherwise): ``self.rival`` is a
+    ``net.clone()``, refreshed with ``rival.copy_from(net)`` after every K-th
+    optimisation step -- self-play against a frozen copy of oneself.  With a
+    network as ship 1 ``explore`` applies to both ships, and both ships'
+    experiences go to the ring as before."""
 
     def __init__(self, env, net, buf, explore, n_samples=1024, n_ministeps=1, lr=1e-2, seed=0,
-                 optimizer=None, target_sync=None, double=False, opponent=None):
+                 optimizer=None, target_sync=None, double=False, opponent=None, opponent_sync=None):
         if buf.n_env != env.n_env or buf.nships != env.S:
             raise ValueError('the replay buffer is [%d envs, %d ships], the env [%d, %d]'
                              % (buf.n_env, buf.nships, env.n_env, env.S))
@@ -56,7 +65,22 @@ class QTrainer:
             else:
                 raise ValueError('target_sync must be an int >= 1 (steps between hard copies) or a float in (0, 1)')
             self.target = net.clone()
-        env._check_opponent(opponent)
+        self.rival, self.rival_every = None, None
+        if isinstance(opponent, str) and opponent == 'snapshot':
+            if not (isinstance(opponent_sync, int) and not isinstance(opponent_sync, bool) and opponent_sync >= 1):
+                raise ValueError("opponent='snapshot' needs opponent_sync, an int >= 1 (optimisation steps "
+                                 'between refreshes)')
+            if env.S != 2:
+                raise ValueError('opponent needs a two-ship env')
+            self.rival, self.rival_every = net.clone(), opponent_sync
+        else:
+            if opponent_sync is not None:
+                raise ValueError("opponent_sync goes with opponent='snapshot' only")
+            env._check_opponent(opponent)
+            if opponent is not None and not isinstance(opponent, str):
+                self.rival = opponent
+        # what env.qcontrols takes, and the scripted name whose controls fill ship 1's column
+        self._acting, self._bot = env._with_opponent(net, opponent if self.rival is None else self.rival)
 
     def _targets(self, r, d, nf, term):
         valuer = self.net if self.target is None else self.target
@@ -79,9 +103,9 @@ class QTrainer:
         env, net, buf = self.env, self.net, self.buf
         t = buf.t
         env.features(out=buf.head())
-        control = env.qcontrols(net, tick0=t, explore=self.explore)
-        if self.opponent is not None:
-            control[:, 1] = env.controls(self.opponent, self.seed, t)[:, 1]
+        control = env.qcontrols(self._acting, tick0=t, explore=self.explore)
+        if self._bot is not None:
+            control[:, 1] = env.controls(self._bot, self.seed, t)[:, 1]
         _, reward, done = env.step(control)
         buf.push(control, reward, done)
         if buf.eligible_lower_bound() < self.n_samples:
@@ -93,6 +117,8 @@ class QTrainer:
             loss = self._step(f, a, self._targets(r, d, nf, term))
             buf.update_loss(ids, loss)
             self.nstep += 1
+            if self.rival_every is not None and self.nstep % self.rival_every == 0:
+                self.rival.copy_from(net)
             out = dict(loss=loss.sum(), n=torch.full((), ids.shape[0], dtype=torch.int32, device=loss.device))
         self.last = out
         return out
@@ -109,5 +135,6 @@ class QTrainer:
         opponent, games)`` with the greedy network from the env's current
         states, as ``actor.Episodes.summary()`` -- the share of games won by
         each ship (ship 0 is the network), the share without a winner and the
-        median length in ticks.  Synchronises."""
+        median length in ticks.  opponent: None, a scripted bot's name or a
+        ``QNetwork`` (``self.rival``, say) as ship 1.  Synchronises."""
         return eval_env._play_q(self.net, opponent, games, None, None, 0).summary()

@@ -12,11 +12,14 @@ per step, SGD with lr 1e-2).  The evaluation envs are re-created with the same
 seeds before every validation, so every point of the curve plays the same
 games.  --optimizer, --target-sync, --double, --opponent, --max-norm and
 --weight-decay select QTrainer's options (astro_amd.optim); without them the
-run is the one described above.  The settings are part of the arguments the
-curve file records.
+run is the one described above.  --opponent snapshot --opponent-sync K trains
+against a frozen copy of the network, refreshed every K optimisation steps.  The
+settings are part of the arguments the curve file records.
 
 Writes one JSON document to --out: the arguments, and per validation the tick,
-the optimisation steps so far, the last loss per sample and both summaries.  No
+the optimisation steps so far, the last loss per sample, both summaries and,
+after tick 0, the network against its copy from the previous validation and
+against the tick-0 network (league.compare: both seats, wins and p_better).  No
 result is expected of it: it reports what the budget gave.
 """
 import argparse
@@ -29,7 +32,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
-from astro_amd import BatchedEnv, DEFAULT_CONFIG, ReplayBuffer, actor, optim, qnet, train  # noqa: E402
+from astro_amd import BatchedEnv, DEFAULT_CONFIG, ReplayBuffer, actor, league, optim, qnet, train  # noqa: E402
 
 
 def main():
@@ -52,8 +55,10 @@ def main():
     ap.add_argument('--target-sync', default=None,
                     help='an integer K: a target network hard-copied every K steps; a float in (0, 1): Polyak tau')
     ap.add_argument('--double', action='store_true', help='Double-DQN targets')
-    ap.add_argument('--opponent', choices=('script', 'nothing', 'random'), default=None,
-                    help='ship 1 of the training envs plays this bot instead of the network')
+    ap.add_argument('--opponent', choices=('script', 'nothing', 'random', 'snapshot'), default=None,
+                    help='ship 1 of the training envs plays this bot instead of the network; snapshot: a frozen copy '
+                         'of the network, refreshed every --opponent-sync optimisation steps')
+    ap.add_argument('--opponent-sync', type=int, default=None, help='with --opponent snapshot: steps between refreshes')
     ap.add_argument('--max-norm', type=float, default=None, help='clip the gradient norm to this')
     ap.add_argument('--weight-decay', type=float, default=0.0)
     args = ap.parse_args()
@@ -75,10 +80,16 @@ def main():
                'rmsprop': lambda: optim.RMSprop(**common), 'adagrad': lambda: optim.Adagrad(**common),
                'adam': lambda: optim.Adam(**common)}[args.optimizer]()
     tr = train.QTrainer(env, net, buf, eg, n_samples=args.n_samples, lr=args.lr, seed=args.seed, optimizer=opt,
-                        target_sync=sync, double=args.double, opponent=args.opponent)
+                        target_sync=sync, double=args.double, opponent=args.opponent, opponent_sync=args.opponent_sync)
     eval_cfg = DEFAULT_CONFIG._replace(max_time=args.max_time)
     curve = []
     t0 = time.time()
+    first, previous = net.clone(), net.clone()     # the network at tick 0 and at the validation before this one
+
+    def against(other):
+        ev = BatchedEnv(eval_cfg, args.eval_envs, device=dev, b_cap=32, env_offset=1 << 20)
+        ev.reset()
+        return league.compare(ev, net, other, games=args.games)
 
     def validate(tick):
         point = dict(tick=tick, nstep=tr.nstep, seconds=round(time.time() - t0, 2),
@@ -90,6 +101,9 @@ def main():
             ev = BatchedEnv(eval_cfg, args.eval_envs, device=dev, b_cap=32, env_offset=1 << 20)
             ev.reset()
             point[opponent] = tr.validate(ev, games=args.games, opponent=opponent)
+        if tick:
+            point['vs_previous'], point['vs_first'] = against(previous), against(first)
+            previous.copy_from(net)
         curve.append(point)
         print(json.dumps(point), flush=True)
 
