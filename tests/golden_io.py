@@ -20,6 +20,14 @@ def configs():
     return {k: Config(**v) for k, v in raw.items()}
 
 
+def wide_configs():
+    """mp11, mp16 and mp16_solo of wide.npz (tools/gen_golden.py: gen_wide):
+    more than 8 planets, so they stay out of configs.json, whose names
+    parametrise tests that run with 8 planet slots."""
+    raw = json.loads(str(load('wide.npz')['configs']))
+    return {k: Config(**v) for k, v in raw.items()}
+
+
 def load(name):
     """np.load of a fixture.  A fixture too large for one committed file is
     stored as consecutive byte ranges name.00, name.01, ... (tools/
@@ -118,8 +126,8 @@ class Features:
     """rl.ValueNetwork.get_features of every input state of steps.npz, and a
     few to_batch results (tools/gen_golden.py: gen_features)."""
 
-    def __init__(self):
-        z = load('features.npz')
+    def __init__(self, fname='features.npz'):
+        z = load(fname)
         self.z = {k: z[k] for k in z.files}
 
     def of(self, i):

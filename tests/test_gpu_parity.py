@@ -292,10 +292,18 @@ def test_irregular_fire_schedule(kernel):
     _auto_reset_vs_oracle(cfg, 'reload0.33', 600, 60, 32, kernel)
 
 
-def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True):
+def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True, p_pad=8, dtype=torch.float32,
+                          prepare=None, record=None):
+    """prepare(env): called on the new env before its reset (tests/test_gpu_planet_slots.py puts its
+    planets behind guards).  record: a dict that receives the env, the games each env played and the
+    oracle's own counts (the planet counts seen, planet slots read, collisions)."""
     P = batched.make_params(cfg)
-    env = _env(cfg, n, dtype=torch.float32, b_cap=bcap, auto_reset=True, kernel=kernel)
+    store = 'f32' if dtype == torch.float32 else 'f64'
+    env = _env(cfg, n, dtype=dtype, b_cap=bcap, p_pad=p_pad, auto_reset=True, kernel=kernel)
+    if prepare is not None:
+        prepare(env)
     env.reset()
+    counts_seen, planets_read, collisions = set(), 0, 0
     seeds = batched.game_seeds(env.stream_seeds, 64)
     games = np.ones(n, np.int64)          # game 0 was created by reset()
     rng = np.random.RandomState(1)
@@ -304,10 +312,13 @@ def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True):
     for t in range(ticks):
         B = _host_batch(env)
         ctl = rng.randint(0, 6, size=(n, env.S)).astype(np.int8)
-        want, wrew, wdone = batched.step(B, ctl, P, store='f32')
+        want, wrew, wdone = batched.step(B, ctl, P, store=store)
+        counts_seen.update(B.nplanets.tolist())
+        planets_read += int(B.nplanets.sum())
+        collisions += int((wdone == 1).sum())
         fin = np.nonzero(wdone)[0]
         if fin.size:
-            fresh = batched.create(seeds[fin, games[fin]], P, p_pad=env.p_pad, b_cap=bcap, store='f32')
+            fresh = batched.create(seeds[fin, games[fin]], P, p_pad=env.p_pad, b_cap=bcap, store=store)
             want.put(fin, fresh)
             games[fin] += 1
         _, rew, done = env.step(torch.from_numpy(ctl).cuda(), stats=stats)
@@ -315,13 +326,16 @@ def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True):
         assert (done == wdone).all(), t
         assert np.array_equal(rew.cpu().numpy(), wrew), t
         got = _host_batch(env)
-        _assert_same('%s t=%d' % (name, t), got, want, np.ones(n, bool), rounding=True)
+        _assert_same('%s t=%d' % (name, t), got, want, np.ones(n, bool), rounding=dtype == torch.float32)
         assert (got.overflow == want.overflow).all(), t
         saw_overflow |= bool(want.overflow.any())
         nb16 = np.pad(B.nbullets, (0, -n % 16)).reshape(-1, 16).sum(1)
         max_wave_bullets = max(max_wave_bullets, int(nb16.max()))
     assert games.max() > 1
     st = env.stat_dict()
+    if record is not None:
+        record.update(env=env, games=games, stats=st, counts_seen=counts_seen, planets_read=planets_read,
+                      collisions=collisions)
     if stats:
         assert st['resets'] == int((games - 1).sum())
     else:   # (the counter-free instance leaves the stats rows alone)

@@ -11,7 +11,9 @@ Test infrastructure only.  This script imports DouglasOrr/Astro's own
 ``to_batch`` (rl.py:36-112), ``rl.ValueNetwork.forward`` (rl.py:137-155) and
 ``rl.QBotTrainer``'s experience bookkeeping (rl.py:249-258, 303-328) and
 counts of ``rl.EpsilonGreedy``'s transitions (rl.py:10-29),
-as small ``.npz``/``.json`` fixtures.
+as small ``.npz``/``.json`` fixtures.  ``wide.npz`` (``gen_wide``) holds
+create, steps, ScriptBot decisions and features of configs with 11 and 16
+planets; ``python tools/gen_golden.py wide`` rewrites it alone, byte for byte.
 
 It refuses to run when ``/root/reference`` is absent, so it never runs on the
 GPU box; the fixtures it writes are plain data (inputs + expected outputs) and
@@ -70,14 +72,14 @@ def cfg_json():
 # ---------------------------------------------------------------------------
 # State <-> padded arrays
 
-def pack_state(state, nships):
+def pack_state(state, nships, p_pad=P_PAD):
     """Reference State -> padded float64 arrays + counts + dtype flags."""
     ships = np.zeros((S_PAD, 5))
     ships[:nships, 0:2] = state.ships.x
     ships[:nships, 2:4] = state.ships.dx
     ships[:nships, 4] = state.ships.b
     npl = state.planets.x.shape[0]
-    planets = np.zeros((P_PAD, 4))
+    planets = np.zeros((p_pad, 4))
     planets[:npl, 0:2] = state.planets.x
     planets[:npl, 2:4] = state.planets.dx
     bullets = np.concatenate([state.bullets.x, state.bullets.dx], axis=1).astype(np.float64)
@@ -107,27 +109,29 @@ def round_state(state):
 class TransitionWriter:
     """Ragged store of teacher-forced (state_in, control) -> ref outputs."""
 
-    def __init__(self):
+    def __init__(self, configs=None, p_pad=P_PAD):
         self.rows = []
+        self.configs = CONFIGS if configs is None else configs
+        self.p_pad = p_pad
 
     def add(self, cfg_name, tick, state_in, control, config):
         nships = state_in.ships.x.shape[0]
         out_state, reward = core.step(state_in, np.asarray(control), config)
-        ships, planets, npl, bullets, flags = pack_state(state_in, nships)
+        ships, planets, npl, bullets, flags = pack_state(state_in, nships, self.p_pad)
         if out_state is None:
             done = 1 if reward.dtype.kind == 'i' else 2
             o_ships = np.zeros((S_PAD, 5))
-            o_planets = np.zeros((P_PAD, 4))
+            o_planets = np.zeros((self.p_pad, 4))
             o_bullets = np.zeros((0, 4))
         else:
             done = 0
-            o_ships, o_planets, _, o_bullets, _ = pack_state(out_state, nships)
+            o_ships, o_planets, _, o_bullets, _ = pack_state(out_state, nships, self.p_pad)
         rew = np.zeros(S_PAD)
         rew[:nships] = reward
         ctl = np.full(S_PAD, 2, dtype=np.int64)
         ctl[:nships] = control
         self.rows.append(dict(
-            cfg=list(CONFIGS).index(cfg_name), tick=tick, nships=nships,
+            cfg=list(self.configs).index(cfg_name), tick=tick, nships=nships,
             nplanets=npl, flags=flags, ships=ships, planets=planets,
             bullets=bullets, control=ctl, done=done, reward=rew,
             reward_int=int(reward.dtype.kind == 'i'),
@@ -135,6 +139,10 @@ class TransitionWriter:
         return out_state, reward
 
     def save(self, path):
+        np.savez_compressed(path, **self.arrays())
+        print('wrote', path, len(self.rows), 'transitions')
+
+    def arrays(self):
         R = self.rows
 
         def ragged(key):
@@ -145,8 +153,7 @@ class TransitionWriter:
             return flat, off
         bi, bio = ragged('bullets')
         bo, boo = ragged('o_bullets')
-        np.savez_compressed(
-            path,
+        return dict(
             cfg=np.array([r['cfg'] for r in R], dtype=np.int32),
             tick=np.array([r['tick'] for r in R], dtype=np.int32),
             nships=np.array([r['nships'] for r in R], dtype=np.int32),
@@ -162,9 +169,8 @@ class TransitionWriter:
             out_ships=np.stack([r['o_ships'] for r in R]),
             out_planets=np.stack([r['o_planets'] for r in R]),
             out_bullets=bo, out_bullets_off=boo,
-            cfg_names=np.array(list(CONFIGS)),
+            cfg_names=np.array(list(self.configs)),
         )
-        print('wrote', path, len(R), 'transitions')
 
 
 # ---------------------------------------------------------------------------
@@ -853,7 +859,174 @@ def gen_explore(seeds=8, ticks=200000, game=1500, dt=0.02):
     print('wrote explore.npz', {k: v.sum(0).tolist() for k, v in out.items()})
 
 
+# ---------------------------------------------------------------------------
+# 15. More than 8 planets: create, teacher-forced steps, ScriptBot decisions
+#     and get_features at max_planets 11 and 16 (wide.npz, 16 planet slots).
+#     These configs stay out of configs.json: sorted(configs.json) parametrises
+#     tests that run with 8 planet slots.
+
+WIDE_P_PAD = 16
+WIDE_CONFIGS = {
+    'mp11': core.DEFAULT_CONFIG._replace(max_planets=11),   # randint's rejection path above 8
+    'mp16': core.DEFAULT_CONFIG._replace(max_planets=16),
+    'mp16_solo': core.SOLO_CONFIG._replace(max_planets=16),
+}
+
+
+def save_npz_fixed(path, arrays):
+    """np.savez_compressed with a fixed member date, so that the same arrays
+    give the same bytes on every run (numpy stamps each member with the
+    current time)."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as zf:
+        for key, val in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            info = zipfile.ZipInfo(key + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o600 << 16
+            zf.writestr(info, buf.getvalue())
+
+
+def _wide_create_seeds(base, per_count):
+    """Seeds of generate_configs(base), the first per_count of each planet
+    count 1..max_planets (create()'s first draw, core.py:90), in stream order."""
+    mp = base.max_planets
+    have = {k: 0 for k in range(1, mp + 1)}
+    seeds = []
+    for c in it.islice(core.generate_configs(base), 20000):
+        n = int(np.random.RandomState(c.seed).randint(1, mp + 1))
+        if have[n] < per_count:
+            have[n] += 1
+            seeds.append(c.seed)
+        if all(v == per_count for v in have.values()):
+            return seeds
+    raise RuntimeError('not every planet count found')
+
+
+def _wide_games(base, counts):
+    """For each planet count of ``counts``, the next config of
+    generate_configs(base) whose create() draws that many planets."""
+    stream = core.generate_configs(base)
+    for want in counts:
+        for c in stream:
+            if int(np.random.RandomState(c.seed).randint(1, base.max_planets + 1)) == want:
+                yield c
+                break
+
+
+def _planet_collision(state, ctl, config):
+    """True if core.step ends this state with a ship inside a planet's radius."""
+    nxt, reward = core.step(state, ctl, config)
+    if nxt is not None or reward.dtype.kind != 'i':
+        return False
+    d = state.ships.x[:, None, :].astype(np.float64) - state.planets.x[None, :, :].astype(np.float64)
+    return bool(((d ** 2).sum(-1) < (config.ship_radius + config.planet_radius) ** 2).any())
+
+
+def gen_wide():
+    rl = _import_rl()
+    out = dict(configs=np.array(json.dumps({k: dict(v._asdict()) for k, v in WIDE_CONFIGS.items()})),
+               numpy=np.array(np.__version__))
+    # create(): every planet count 1..max_planets, about 64 seeds per config
+    for name, base in WIDE_CONFIGS.items():
+        mp = base.max_planets
+        seeds = _wide_create_seeds(base, -(-64 // mp))
+        k = len(seeds)
+        npl = np.zeros(k, dtype=np.int32)
+        sx = np.zeros((k, S_PAD, 2), np.float32)
+        sdx = np.zeros((k, S_PAD, 2), np.float32)
+        sb = np.zeros((k, S_PAD), np.float32)
+        px = np.zeros((k, WIDE_P_PAD, 2), np.float32)
+        pdx = np.zeros((k, WIDE_P_PAD, 2), np.float64)
+        first = np.zeros(k, dtype=np.uint32)
+        for i, seed in enumerate(seeds):
+            s = core.create(base._replace(seed=seed))
+            n = s.ships.x.shape[0]
+            assert s.ships.x.dtype == np.float32 and s.ships.b.dtype == np.float32
+            npl[i] = s.planets.x.shape[0]
+            sx[i, :n] = s.ships.x
+            sdx[i, :n] = s.ships.dx
+            sb[i, :n] = s.ships.b
+            px[i, :npl[i]] = s.planets.x
+            pdx[i, :npl[i]] = s.planets.dx
+            first[i] = np.random.RandomState(seed).randint(0, 1 << 32, dtype=np.uint64)
+        assert set(npl.tolist()) == set(range(1, mp + 1)), name
+        if name == 'mp11':   # randint(1, 12): word & 15 until <= 10
+            assert ((first & 15) > 10).sum() >= 3
+        for key, val in dict(seed=np.array(seeds, dtype=np.uint32), first_word=first, nplanets=npl, ships_x=sx,
+                             ships_dx=sdx, ships_b=sb, planets_x=px, planets_dx=pdx).items():
+            out['%s__%s' % (name, key)] = val
+
+    # teacher-forced transitions along reference games
+    w = TransitionWriter(WIDE_CONFIGS, WIDE_P_PAD)
+    plan = [
+        # (config, policy, games, keep_every)
+        ('mp11', 'random', 6, 12),
+        ('mp11', 'script', 2, 24),
+        ('mp16', 'random', 8, 12),
+        ('mp16', 'script', 3, 24),
+        ('mp16', 'nothing', 2, 16),
+        ('mp16_solo', 'random', 4, 12),
+        ('mp16_solo', 'script', 2, 48),
+    ]
+    planet_ends = 0
+    for cfg_name, policy, games, keep in plan:
+        base = WIDE_CONFIGS[cfg_name]
+        # game g has the g-th planet count of this walk: full slots first, then down through the rest
+        mp = base.max_planets
+        counts = [mp, 9, mp - 1, 1, 12 if mp > 12 else 10, 5, mp, 3, 13 if mp > 12 else 8, 2, 10, 7, 14 if mp > 12 else 6, 4]
+        for g, config in enumerate(_wide_games(base, counts[:games])):
+            rng = np.random.RandomState(3000 + g)
+            nships = 1 if config.solo else 2
+            bots = [script.ScriptBot.create(config) for _ in range(nships)]
+            state = core.create(config)
+            tick = 0
+            while state is not None and tick < 400:
+                ctl = _controls(policy, rng, nships, state, bots)
+                nb_before = state.bullets.x.shape[0]
+                nxt, reward = core.step(state, ctl, config)
+                interesting = (tick == 0 or nxt is None or nxt.bullets.x.shape[0] != nb_before)
+                if interesting or tick % keep == 0:
+                    rs = round_state(state)
+                    w.add(cfg_name, tick, rs, ctl, config)
+                    planet_ends += _planet_collision(rs, np.asarray(ctl), config)
+                state = nxt
+                tick += 1
+    tr = w.arrays()
+    assert planet_ends > 0 and (tr['tick'] == 0).any() and np.diff(tr['in_bullets_off']).max() > 0
+    assert tr['nplanets'].max() == 16 and (tr['nplanets'][tr['cfg'] == 0] > 8).any()
+    out.update(tr)
+
+    # the reference ScriptBot's decision for every ship, and get_features, of every input state
+    n = tr['tick'].shape[0]
+    names = list(WIDE_CONFIGS)
+    ctl = np.full((n, S_PAD), -1, dtype=np.int8)
+    bots = {k: script.ScriptBot.create(v) for k, v in WIDE_CONFIGS.items()}
+    feats = []
+    for i in range(n):
+        state = _steps_state(tr, i)
+        for k in range(int(tr['nships'][i])):
+            ctl[i, k] = bots[names[tr['cfg'][i]]](core.roll_ships(state, k))
+        f = rl.ValueNetwork.get_features(state)
+        assert f.dtype == np.float32
+        feats.append(f)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum([f.shape[0] for f in feats])
+    flat = np.zeros((int(off[-1]), 15), dtype=np.float32)
+    for i, f in enumerate(feats):
+        flat[off[i]:off[i + 1], :f.shape[1]] = f
+    out.update(script_control=ctl, features=flat, features_off=off,
+               dims=np.array([f.shape[1] for f in feats], dtype=np.int32))
+    save_npz_fixed(os.path.join(OUT, 'wide.npz'), out)
+    print('wrote wide.npz', n, 'transitions,', planet_ends, 'end by a planet collision,', int(off[-1]),
+          'feature rows,', os.path.getsize(os.path.join(OUT, 'wide.npz')), 'bytes')
+
+
 def generate():
+    if sys.argv[1:] == ['wide']:
+        gen_wide()
+        return
     if sys.argv[1:] == ['explore']:
         gen_explore()
         return
@@ -896,6 +1069,7 @@ def generate():
     gen_long_games()
     gen_replay()
     gen_explore()
+    gen_wide()
 
 
 # No committed file may exceed 1 MiB: a larger fixture is stored as consecutive
