@@ -171,17 +171,28 @@ typedef struct AstroPolicy {
  * [ceil(n_env / 16)][ASTRO_NSTATS], one private row per wave64 (a wave covers
  * 64 envs in the LANE kernel, 16 in the QUAD kernel), added to and never
  * cleared by the library.  Sum the rows for totals.  (A private row per wave keeps the counters contention-free:
- * every wave adding into one shared row serialises at the memory side.) */
+ * every wave adding into one shared row serialises at the memory side.)
+ * Every counter is a sum over envs and ticks, the same in the LANE, QUAD and
+ * PAIR kernels and in astro_step, astro_step_many and astro_rollout.  An env
+ * whose game ends this tick (collision or timeout) still counts the bullets and
+ * planets it read, but writes no next state: it adds nothing to BULLETS_OUT or
+ * OVERFLOWS, and the game auto-reset creates in its place has no bullets. */
 enum {
-    ASTRO_STAT_BULLETS_IN = 0,  /* live bullets read */
-    ASTRO_STAT_BULLETS_OUT = 1, /* live bullets written */
+    ASTRO_STAT_BULLETS_IN = 0,  /* live bullets read: the env's bullet count at the tick's start,
+                                   whether its game goes on or ends */
+    ASTRO_STAT_BULLETS_OUT = 1, /* live bullets written: the next state's bullet count (survivors
+                                   plus kept shots, at most b_cap) of an env that goes on */
     ASTRO_STAT_RESETS = 2,      /* envs re-created by auto-reset */
     ASTRO_STAT_COLLISIONS = 3,  /* games ended by a ship collision */
     ASTRO_STAT_TIMEOUTS = 4,    /* games ended by max_time */
-    ASTRO_STAT_OVERFLOWS = 5,   /* bullets dropped for lack of b_cap */
-    ASTRO_STAT_PLANETS = 6,     /* planet slots read */
+    ASTRO_STAT_OVERFLOWS = 5,   /* bullets dropped for lack of b_cap: kept candidates (survivors,
+                                   then shots) beyond b_cap, of an env that goes on */
+    ASTRO_STAT_PLANETS = 6,     /* planet slots read: the env's planet count, whether its game
+                                   goes on or ends */
     ASTRO_STAT_SERIAL = 7,      /* resets the QUAD/PAIR kernels could not make in their
-                                   wave-cooperative pass (serial create) */
+                                   wave-cooperative pass (serial create): a rejected randint
+                                   word, or a game that ends at its first step, before its
+                                   next seed was drawn; 0 in the LANE kernel */
     ASTRO_NSTATS = 8
 };
 

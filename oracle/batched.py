@@ -170,10 +170,17 @@ def _floor_divmod2(c):
     return c // 2, c % 2
 
 
-def step(st, control, P, store='f32'):
+def step(st, control, P, store='f32', counts=None):
     """One tick for every env of ``st``.  Returns (new Batch, reward f32[N,S],
     done u8[N]) with done = 0 running, 1 ship collision, 2 timeout.  Envs that
-    finish keep their input state (the caller resets them)."""
+    finish keep their input state (the caller resets them).
+
+    ``counts``: a dict that receives this tick's per-env counts, int64[N] each,
+    as include/astro_step.h defines the library's statistics: ``bullets_in``
+    (bullets read), ``bullets_out`` (bullets written: 0 for an env that
+    finishes), ``overflows`` (kept candidates beyond the bullet capacity, 0 for
+    an env that finishes), ``planets`` (planet slots read), ``collisions`` and
+    ``timeouts`` (0/1).  The results are the same with and without it."""
     N, S = st.ships.shape[:2]
     Pp, Bc = st.planets.shape[1], st.bullets.shape[1]
     t0 = st.tick == 0
@@ -294,6 +301,11 @@ def step(st, control, P, store='f32'):
             sel = sel[:Bc]
         nnew[i] = sel.size
         newb[i, :sel.size] = np.stack([mx[i, sel], my[i, sel], mdx[i, sel], mdy[i, sel]], -1)
+    if counts is not None:
+        kept = keep.sum(1).astype(np.int64)
+        counts.update(bullets_in=st.nbullets.astype(np.int64), bullets_out=np.where(run, nnew, 0).astype(np.int64),
+                      overflows=np.where(run, np.maximum(kept - Bc, 0), 0), planets=st.nplanets.astype(np.int64),
+                      collisions=(done == 1).astype(np.int64), timeouts=(done == 2).astype(np.int64))
 
     r = run
     out.ships[r] = np.stack([nx, ny, ndx, ndy], -1)[r]

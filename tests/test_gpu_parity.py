@@ -296,7 +296,8 @@ def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True, p_pad=8
                           prepare=None, record=None):
     """prepare(env): called on the new env before its reset (tests/test_gpu_planet_slots.py puts its
     planets behind guards).  record: a dict that receives the env, the games each env played and the
-    oracle's own counts (the planet counts seen, planet slots read, collisions)."""
+    oracle's own counts (the planet counts seen, planet slots read, collisions).  With stats on, the
+    library's bullets_in, bullets_out, overflows, collisions and timeouts equal the oracle's sums."""
     P = batched.make_params(cfg)
     store = 'f32' if dtype == torch.float32 else 'f64'
     env = _env(cfg, n, dtype=dtype, b_cap=bcap, p_pad=p_pad, auto_reset=True, kernel=kernel)
@@ -304,6 +305,8 @@ def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True, p_pad=8
         prepare(env)
     env.reset()
     counts_seen, planets_read, collisions = set(), 0, 0
+    # the oracle's sums over the run of what include/astro_step.h's statistics count
+    oracle_counts = dict.fromkeys(('bullets_in', 'bullets_out', 'overflows', 'collisions', 'timeouts'), 0)
     seeds = batched.game_seeds(env.stream_seeds, 64)
     games = np.ones(n, np.int64)          # game 0 was created by reset()
     rng = np.random.RandomState(1)
@@ -312,7 +315,10 @@ def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True, p_pad=8
     for t in range(ticks):
         B = _host_batch(env)
         ctl = rng.randint(0, 6, size=(n, env.S)).astype(np.int8)
-        want, wrew, wdone = batched.step(B, ctl, P, store=store)
+        tick_counts = {}
+        want, wrew, wdone = batched.step(B, ctl, P, store=store, counts=tick_counts)
+        for c in oracle_counts:
+            oracle_counts[c] += int(tick_counts[c].sum())
         counts_seen.update(B.nplanets.tolist())
         planets_read += int(B.nplanets.sum())
         collisions += int((wdone == 1).sum())
@@ -338,6 +344,9 @@ def _auto_reset_vs_oracle(cfg, name, n, ticks, bcap, kernel, stats=True, p_pad=8
                       collisions=collisions)
     if stats:
         assert st['resets'] == int((games - 1).sum())
+        for c, v in oracle_counts.items():
+            assert st[c] == v, (c, st[c], v)
+        assert oracle_counts['collisions'] == collisions
     else:   # (the counter-free instance leaves the stats rows alone)
         assert not any(st.values())
     if name == 'rapid' and bcap < 10:
