@@ -28,6 +28,67 @@ def wide_configs():
     return {k: Config(**v) for k, v in raw.items()}
 
 
+def world_configs():
+    """The configs of world.npz (tools/gen_golden.py: gen_world): ``world`` and
+    its variants, every physics constant away from DEFAULT_CONFIG's, and one
+    ``only_<field>`` config per constant.  They stay out of configs.json, whose
+    sorted names parametrise other tests."""
+    raw = json.loads(str(load('world.npz')['configs']))
+    return {k: Config(**v) for k, v in raw.items()}
+
+
+# world.npz: the eleven constants, the five configs that change all of them, and
+# the single-field configs whose field create() reads
+WORLD_FIELDS = ('gravity', 'dt', 'bullet_speed', 'ship_thrust', 'ship_rspeed', 'ship_radius', 'planet_radius',
+                'planet_mass', 'planet_orbit', 'inner_ship_position', 'outer_ship_position')
+WORLD_FULL = ('world', 'world_mp8', 'world_one', 'world_solo', 'world_rapid')
+WORLD_CREATED = ('world', 'world_mp8', 'world_one', 'world_solo', 'only_gravity', 'only_planet_mass',
+                 'only_planet_orbit', 'only_inner_ship_position', 'only_outer_ship_position')
+
+
+def world_events(tr, configs):
+    """Per transition of world.npz, from its input state alone (float64
+    arithmetic on the recorded values): which pairs of bodies are within their
+    collision distance, and whether a bullet that is not hit leaves the square
+    on both axes (core.py:195)."""
+    names = [str(x) for x in tr['cfg_names']]
+    n = tr['tick'].shape[0]
+    ev = {k: np.zeros(n, bool) for k in ('ship_ship', 'ship_planet', 'ship_bullet', 'bullet_planet', 'culled')}
+    off = tr['in_bullets_off']
+
+    def d2(a, b):
+        return ((a[:, None, :] - b[None, :, :]) ** 2).sum(-1)
+    for i in range(n):
+        cfg = configs[names[tr['cfg'][i]]]
+        S, npl = int(tr['nships'][i]), int(tr['nplanets'][i])
+        sh = tr['in_ships'][i, :S, 0:2].astype(np.float64)
+        pl = tr['in_planets'][i, :npl, 0:2].astype(np.float64)
+        bl = tr['in_bullets'][off[i]:off[i + 1]].astype(np.float64)
+        ev['ship_ship'][i] = S == 2 and d2(sh[:1], sh[1:])[0, 0] < (2 * cfg.ship_radius) ** 2
+        ev['ship_planet'][i] = (d2(sh, pl) < (cfg.ship_radius + cfg.planet_radius) ** 2).any()
+        ev['ship_bullet'][i] = (d2(sh, bl[:, 0:2]) < cfg.ship_radius ** 2).any()
+        in_planet = (d2(bl[:, 0:2], pl) < cfg.planet_radius ** 2).any(1)
+        hit = in_planet | (d2(bl[:, 0:2], sh) < cfg.ship_radius ** 2).any(1)
+        ev['bullet_planet'][i] = in_planet.any()
+        moved = bl[:, 0:2] + cfg.dt * bl[:, 2:4]
+        ev['culled'][i] = (~hit & (np.abs(moved) > 1).all(1)).any()
+    return ev
+
+
+def world_games():
+    """The whole free-running games of world.npz, as ``games()`` gives games.npz's."""
+    z = load('world.npz')
+    out = []
+    for cfg in WORLD_FULL:
+        for k in range(3):
+            key = 'game_%s_%d' % (cfg, k)
+            g = dict(cfg=cfg, gid=key)
+            for f in ('seed', 'controls', 'ships', 'planets', 'nbullets', 'reward', 'done'):
+                g[f] = z[key + '__' + f]
+            out.append(g)
+    return out
+
+
 def load(name):
     """np.load of a fixture.  A fixture too large for one committed file is
     stored as consecutive byte ranges name.00, name.01, ... (tools/

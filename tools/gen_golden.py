@@ -14,6 +14,9 @@ counts of ``rl.EpsilonGreedy``'s transitions (rl.py:10-29),
 as small ``.npz``/``.json`` fixtures.  ``wide.npz`` (``gen_wide``) holds
 create, steps, ScriptBot decisions and features of configs with 11 and 16
 planets; ``python tools/gen_golden.py wide`` rewrites it alone, byte for byte.
+``world.npz`` (``gen_world``) holds create, steps, ScriptBot decisions, fire
+schedules and whole games of configs with every world constant changed;
+``python tools/gen_golden.py world`` rewrites it alone, byte for byte.
 
 It refuses to run when ``/root/reference`` is absent, so it never runs on the
 GPU box; the fixtures it writes are plain data (inputs + expected outputs) and
@@ -1023,7 +1026,276 @@ def gen_wide():
           'feature rows,', os.path.getsize(os.path.join(OUT, 'wide.npz')), 'bytes')
 
 
+# ---------------------------------------------------------------------------
+# 16. Away from DEFAULT_CONFIG's world constants (world.npz): create,
+#     teacher-forced steps, ScriptBot decisions with their margins, the fire
+#     schedule and whole games under configs whose eleven physics constants are
+#     all inexact in float32 and no power-of-two multiple of their defaults.
+#     These configs stay out of configs.json, as the wide ones do.
+
+WORLD_VALUES = dict(
+    gravity=0.08, dt=0.03, bullet_speed=1.3, ship_thrust=0.7, ship_rspeed=3.3, ship_radius=0.03,
+    planet_radius=0.17, planet_mass=1.3, planet_orbit=0.55, inner_ship_position=0.23, outer_ship_position=0.85)
+_WORLD = core.DEFAULT_CONFIG._replace(reload_time=0.2, **WORLD_VALUES)
+WORLD_CONFIGS = {
+    'world': _WORLD,
+    'world_mp8': _WORLD._replace(max_planets=8),
+    'world_one': _WORLD._replace(max_planets=1),      # the planet stays float32 for ever
+    'world_solo': _WORLD._replace(solo=True, reload_time=1000, max_planets=6),
+    'world_rapid': _WORLD._replace(reload_time=0.02),  # fires at tick 0
+}
+WORLD_CONFIGS.update({'only_' + k: core.DEFAULT_CONFIG._replace(**{k: v}) for k, v in WORLD_VALUES.items()})
+WORLD_FULL = ('world', 'world_mp8', 'world_one', 'world_solo', 'world_rapid')
+WORLD_CREATE_ONLY = ('only_gravity', 'only_planet_mass', 'only_planet_orbit', 'only_inner_ship_position',
+                     'only_outer_ship_position')
+MARGIN_F64, MARGIN_F32, MARGIN_CAP = 1e-9, 1e-5, 0.01
+
+
+def _record_create(out, name, base, seeds, p_pad):
+    k = len(seeds)
+    npl = np.zeros(k, dtype=np.int32)
+    sx = np.zeros((k, S_PAD, 2), np.float32)
+    sdx = np.zeros((k, S_PAD, 2), np.float32)
+    sb = np.zeros((k, S_PAD), np.float32)
+    px = np.zeros((k, p_pad, 2), np.float32)
+    pdx = np.zeros((k, p_pad, 2), np.float64)
+    for i, seed in enumerate(seeds):
+        s = core.create(base._replace(seed=seed))
+        n = s.ships.x.shape[0]
+        assert s.ships.x.dtype == np.float32 and s.ships.b.dtype == np.float32 and s.planets.x.dtype == np.float32
+        npl[i] = s.planets.x.shape[0]
+        sx[i, :n] = s.ships.x
+        sdx[i, :n] = s.ships.dx
+        sb[i, :n] = s.ships.b
+        px[i, :npl[i]] = s.planets.x
+        pdx[i, :npl[i]] = s.planets.dx
+    for key, val in dict(seed=np.array(seeds, dtype=np.uint32), nplanets=npl, ships_x=sx, ships_dx=sdx,
+                         ships_b=sb, planets_x=px, planets_dx=pdx).items():
+        out['%s__%s' % (name, key)] = val
+    return npl, sx, px, pdx
+
+
+def _script_margin(config, state):
+    """The smallest distance of a quantity that script.py:30-91 compares from
+    the threshold it is compared with, along the path ScriptBot takes on this
+    ego view: det and -b + sqrt(det) against 0, distance against the reach,
+    the turn against +-tolerance and its magnitude against pi."""
+    args = script.ScriptBot.DEFAULT_ARGS
+    found = [np.inf]
+
+    def near(value, threshold):
+        found.append(abs(float(value) - float(threshold)))
+
+    def turn(target, tolerance):
+        off = util.norm_angle(target - state.ships.b[0])
+        near(off, -tolerance)
+        near(off, tolerance)
+        near(abs(off), np.pi)
+        return float(np.nanmin(found))
+
+    radius = config.planet_radius + config.ship_radius
+    with np.errstate(all='ignore'):
+        for i in range(state.planets.x.shape[0]):
+            x = state.ships.x[0] - state.planets.x[i]
+            dx = state.ships.dx[0] - state.planets.dx[i]
+            lin = 2 * util.dot(util.norm(dx), x)
+            det = lin ** 2 - 4 * (util.mag(x) ** 2 - (radius + args['avoid_distance']) ** 2)
+            near(det, 0)
+            if 0 < det:
+                near(-lin + np.sqrt(det), 0)
+                if 0 <= -lin + np.sqrt(det):
+                    speed = util.mag(dx)
+                    reach = (speed / config.ship_thrust
+                             + config.ship_rspeed / abs(util.norm_angle(util.bearing(x) - lin))) * speed
+                    near(-lin - np.sqrt(det), reach)
+                    if -lin - np.sqrt(det) < reach:
+                        return turn(util.bearing(x), args['avoid_threshold'])
+        if config.solo:
+            return float(np.nanmin(found))
+        distance = util.mag(state.ships.x[1] - state.ships.x[0])
+        forecast = state.ships.x[1] + distance / config.bullet_speed * (state.ships.dx[1] - state.ships.dx[0])
+        return turn(util.bearing(forecast - state.ships.x[0]), config.ship_radius / distance)
+
+
+def _ram(state):
+    """Both ships turn to each other and thrust: the games that end ship on ship."""
+    out = []
+    for k in range(2):
+        off = util.norm_angle(util.bearing(state.ships.x[1 - k] - state.ships.x[k]) - state.ships.b[k])
+        out.append(1 if off < -0.1 else 5 if off > 0.1 else 3)
+    return np.array(out)
+
+
+def gen_world():
+    out = dict(configs=np.array(json.dumps({k: dict(v._asdict()) for k, v in WORLD_CONFIGS.items()})),
+               numpy=np.array(np.__version__))
+    # create(): every planet count of the four world configs, 16 seeds of the single-field ones
+    for name in ('world', 'world_mp8', 'world_one', 'world_solo'):
+        base = WORLD_CONFIGS[name]
+        mp = base.max_planets
+        npl, sx, px, pdx = _record_create(out, name, base, _wide_create_seeds(base, -(-64 // mp)), P_PAD)
+        assert set(npl.tolist()) == set(range(1, mp + 1)), name
+        if mp > 1:
+            # both ship arrangements of core.py:97-107 (ship 0 outer / inner) and both orbit directions
+            outer0 = np.abs(sx[npl > 1, 0, 0]) == np.float32(base.outer_ship_position)
+            spin = np.sign(px[npl > 1, 0, 0] * pdx[npl > 1, 0, 1] - px[npl > 1, 0, 1] * pdx[npl > 1, 0, 0])
+            assert outer0.any() and not outer0.all() and set(spin.tolist()) == {-1.0, 1.0}, name
+    for name in WORLD_CREATE_ONLY:
+        base = WORLD_CONFIGS[name]
+        _record_create(out, name, base, [c.seed for c in it.islice(core.generate_configs(base), 16)], P_PAD)
+
+    # teacher-forced transitions along reference games
+    w = TransitionWriter(WORLD_CONFIGS, P_PAD)
+    plan = [
+        # (config, policy, planet counts of the games, keep_every, last tick)
+        ('world', 'random', [4, 1, 3, 2, 4, 3, 2], 8, 600),
+        ('world', 'script', [4, 2, 3, 1], 10, 600),
+        ('world', 'nothing', [3, 2], 12, 600),
+        ('world', 'ram', [2, 3, 4, 2, 3, 4], 40, 600),
+        ('world_mp8', 'random', [8, 1, 7, 2, 6, 3, 5, 4], 8, 600),
+        ('world_mp8', 'script', [8, 5, 7, 6, 3, 2], 12, 600),
+        ('world_mp8', 'nothing', [8, 4], 12, 600),
+        ('world_one', 'random', [1, 1, 1], 8, 300),
+        ('world_one', 'script', [1], 12, 300),
+        ('world_one', 'nothing', [1], 12, 300),
+        ('world_solo', 'random', [6, 1, 5, 2, 4, 3, 6, 3, 1, 5], 8, 600),
+        ('world_solo', 'script', [6, 3], 40, 1 << 20),    # to the timeout
+        ('world_solo', 'nothing', [2], 12, 600),
+        ('world_rapid', 'random', [4, 1, 3, 2, 4, 3, 2, 1], 1, 13),
+        ('world_rapid', 'script', [4, 3], 1, 13),
+    ]
+    for name in WORLD_CONFIGS:
+        if name.startswith('only_'):
+            mp = WORLD_CONFIGS[name].max_planets
+            plan += [(name, 'random', [mp, 2], 8, 240), (name, 'script', [3, 4], 8, 240)]
+    for cfg_name, policy, counts, keep, last in plan:
+        base = WORLD_CONFIGS[cfg_name]
+        for g, config in enumerate(_wide_games(base, counts)):
+            rng = np.random.RandomState(7000 + g)
+            nships = 1 if config.solo else 2
+            bots = [script.ScriptBot.create(config) for _ in range(nships)]
+            state = core.create(config)
+            tick = 0
+            while state is not None and tick <= last:
+                ctl = _ram(state) if policy == 'ram' else _controls(policy, rng, nships, state, bots)
+                nb_before = state.bullets.x.shape[0]
+                nxt, reward = core.step(state, ctl, config)
+                interesting = (tick == 0 or nxt is None or nxt.bullets.x.shape[0] != nb_before)
+                if interesting or tick % keep == 0:
+                    w.add(cfg_name, tick, round_state(state), ctl, config)
+                state = nxt
+                tick += 1
+    tr = w.arrays()
+    n = tr['tick'].shape[0]
+    names = list(WORLD_CONFIGS)
+
+    # what the set is for (the events are told from the input states by the tests' own rule)
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+    from tests.golden_io import world_events
+    ev = world_events(tr, WORLD_CONFIGS)
+    nin, nout = np.diff(tr['in_bullets_off']), np.diff(tr['out_bullets_off'])
+    done = tr['out_done']
+    full = np.isin(tr['cfg'], [names.index(k) for k in WORLD_FULL])
+    rapid = tr['cfg'] == names.index('world_rapid')
+    assert (full & (tr['tick'] == 0)).sum() >= 20
+    assert (rapid & (tr['tick'] == 0) & (done == 0) & (nout > 0)).sum() >= 4, 'no fire at tick 0'
+    assert (full & (nin > 0)).sum() > 200
+    for what in ('ship_ship', 'ship_planet', 'ship_bullet'):
+        assert (full & (done == 1) & ev[what]).any(), what
+    assert (full & (done == 2)).any(), 'no timeout'
+    assert (full & (done == 0) & ev['bullet_planet']).any() and (full & (done == 0) & ev['culled']).any()
+    for k in WORLD_FULL:
+        got = set(tr['nplanets'][tr['cfg'] == names.index(k)].tolist())
+        assert got == set(range(1, WORLD_CONFIGS[k].max_planets + 1)), (k, got)
+    per = np.bincount(tr['cfg'], minlength=len(names))
+    assert 1300 <= per[:len(WORLD_FULL)].sum() <= 1700 and (per[len(WORLD_FULL):] >= 40).all(), per
+    assert (per[len(WORLD_FULL):] <= 100).all(), per
+    for key in ('in_ships', 'in_planets', 'in_bullets'):   # float32 values (round_state): stored as such
+        assert np.array_equal(tr[key].astype(np.float32).astype(np.float64), tr[key])
+        tr[key] = tr[key].astype(np.float32)
+    out.update(tr)
+
+    # the reference ScriptBot's decision for every ship of every input state; -2 where its margin is too small
+    ctl = np.full((n, S_PAD), -1, dtype=np.int8)
+    margin = np.full((n, S_PAD), np.inf)
+    bots = {k: script.ScriptBot.create(v) for k, v in WORLD_CONFIGS.items()}
+    for i in range(n):
+        state = _steps_state(tr, i)
+        cfg = WORLD_CONFIGS[names[tr['cfg'][i]]]
+        for k in range(int(tr['nships'][i])):
+            ego = core.roll_ships(state, k)
+            ctl[i, k] = bots[names[tr['cfg'][i]]](ego)
+            margin[i, k] = _script_margin(cfg, ego)
+    limit = np.where(tr['tick'] == 0, MARGIN_F32, MARGIN_F64)[:, None]
+    drop = (ctl >= 0) & (margin < limit)
+    decisions = int((ctl >= 0).sum())
+    assert drop.sum() <= MARGIN_CAP * decisions, (int(drop.sum()), decisions)
+    ctl[drop] = -2
+    out.update(script_control=ctl, script_dropped=np.int64(drop.sum()),
+               script_margin_min=np.float64(margin[(ctl >= 0)].min()))
+
+    # fire ticks and the timeout tick, gen_schedule's way: fire <=> reload was decremented
+    for name, base in WORLD_CONFIGS.items():
+        cfg = base._replace(solo=True, planet_mass=0.0)
+        B = core.Bodies
+        state = core.State(
+            ships=B(x=np.array([[0.9, 0.9]]), dx=np.zeros((1, 2)), b=np.array([0.785])),
+            planets=B(x=np.zeros((1, 2)), dx=np.zeros((1, 2)), b=None),
+            bullets=B(x=np.zeros((0, 2)), dx=np.zeros((0, 2)), b=None), reload=0.0, t=0.0)
+        fires, tick = [], 0
+        while True:
+            nxt, reward = core.step(state, np.array([2]), cfg)
+            if nxt is None:
+                break
+            if nxt.reload != state.reload + cfg.dt:
+                fires.append(tick)
+            state = nxt
+            tick += 1
+        out[name + '__fire_ticks'] = np.array(fires, dtype=np.int32)
+        out[name + '__timeout_tick'] = np.int32(tick)
+
+    # three whole free-running games per world config (gen_games' record)
+    index = []
+    for cfg_name in WORLD_FULL:
+        base = WORLD_CONFIGS[cfg_name]
+        for g, config in enumerate(it.islice(core.generate_configs(base), 200, 203)):
+            nships = 1 if config.solo else 2
+            tmax = int(round(config.max_time / config.dt)) + 2
+            ctl_g = np.random.RandomState(9000 + len(index)).randint(0, 6, size=(tmax, nships))
+            state = core.create(config)
+            ships, nbul, planets = [], [], []
+            tick = 0
+            while state is not None:
+                sp, pp, _, _, _ = pack_state(state, nships)
+                ships.append(sp)
+                planets.append(pp)
+                nbul.append(state.bullets.x.shape[0])
+                state, reward = core.step(state, ctl_g[tick], config)
+                tick += 1
+            rew = np.zeros(2)
+            rew[:nships] = reward
+            key = 'game_%s_%d' % (cfg_name, g)
+            out[key + '__seed'] = np.uint32(config.seed)
+            out[key + '__controls'] = ctl_g[:tick].astype(np.int8)
+            out[key + '__ships'] = np.stack(ships)
+            out[key + '__planets'] = np.stack(planets)
+            out[key + '__nbullets'] = np.array(nbul, dtype=np.int32)
+            out[key + '__reward'] = rew
+            out[key + '__done'] = np.int8(1 if reward.dtype.kind == 'i' else 2)
+            index.append((key, tick))
+    path = os.path.join(OUT, 'world.npz')
+    save_npz_fixed(path, out)
+    size = os.path.getsize(path)
+    assert size < PART_BYTES, size
+    print('wrote world.npz', n, 'transitions', per.tolist(), 'decisions', decisions, 'dropped', int(drop.sum()),
+          'smallest kept margin %.3g' % margin[ctl >= 0].min(), 'games', index, size, 'bytes')
+    print({k: int((full & v).sum()) for k, v in ev.items()}, 'timeouts', int((full & (done == 2)).sum()))
+
+
 def generate():
+    if sys.argv[1:] == ['world']:
+        gen_world()
+        return
     if sys.argv[1:] == ['wide']:
         gen_wide()
         return
@@ -1070,6 +1342,7 @@ def generate():
     gen_replay()
     gen_explore()
     gen_wide()
+    gen_world()
 
 
 # No committed file may exceed 1 MiB: a larger fixture is stored as consecutive
