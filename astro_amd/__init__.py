@@ -7,8 +7,8 @@ exposes the reference's single-game create/step/play surface on top of it;
 ``EpsilonGreedy`` and ``Episodes`` (actor.py) its exploration and per-game
 bookkeeping, ``QTrainer`` (train.py) the training loop made of them, ``SGD``,
 ``RMSprop``, ``Adagrad`` and ``Adam`` (optim.py) its update rules, ``league``
-(league.py) the comparison of two networks: ``p_better``, ``find_better``,
-``compare``.
+(league.py) the comparison of networks: ``p_better``, ``find_better``,
+``compare``, and ``Pool`` / ``tournament`` for many networks on one env.
 """
 from .config import (Bodies, Config, DEFAULT_CONFIG, Game, SOLO_CONFIG,  # noqa: F401
                      SOLO_EASY_CONFIG, State, Tick, generate_configs)
@@ -18,4 +18,4 @@ from .actor import EpsilonGreedy, Episodes  # noqa: F401
 from .optim import SGD, Adagrad, Adam, RMSprop  # noqa: F401
 from .train import QTrainer  # noqa: F401
 from . import league  # noqa: F401
-from .league import compare, find_better, p_better  # noqa: F401
+from .league import Pool, compare, find_better, p_better, tournament  # noqa: F401

@@ -2,7 +2,8 @@
 libastro_qnet.so (include/astro_qnet.h), of libastro_qtrain.so
 (include/astro_qtrain.h), of libastro_replay.so (include/astro_replay.h), of
 libastro_actor.so (include/astro_actor.h), of libastro_qopt.so
-(include/astro_qopt.h) and of libastro_qduel.so (include/astro_qduel.h).
+(include/astro_qopt.h), of libastro_qduel.so (include/astro_qduel.h) and of
+libastro_qpool.so (include/astro_qpool.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -324,6 +325,31 @@ _QDUEL_SYMBOLS = {
 }
 
 
+class AstroQSpan(ctypes.Structure):
+    """include/astro_qpool.h AstroQSpan: ship ``ship`` of the envs [lo, hi) is played by nets[net]."""
+    _fields_ = [
+        ('ship', ctypes.c_int32),
+        ('net', ctypes.c_int32),
+        ('lo', ctypes.c_int32),
+        ('hi', ctypes.c_int32),
+    ]
+
+
+QPOOL_MAX_NETS = 32     # include/astro_qpool.h ASTRO_QPOOL_MAX_NETS
+QPOOL_MAX_SPANS = 64    # ASTRO_QPOOL_MAX_SPANS
+
+# libastro_qpool.so: a pool of Q-networks over blocks of envs, a library of its own (include/astro_qpool.h)
+_QPOOL_SYMBOLS = {
+    'astro_qpool_abi_version': (ctypes.c_int, []),
+    'astro_qpool_last_error': (ctypes.c_char_p, []),
+    'astro_qvalues_pool': (ctypes.c_int, [ctypes.POINTER(AstroParams), ctypes.POINTER(AstroState),
+                                          ctypes.POINTER(AstroQNet), ctypes.c_int32, ctypes.POINTER(AstroQSpan),
+                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.POINTER(AstroPolicy), ctypes.c_double, ctypes.c_int32,
+                                          ctypes.c_void_p]),
+}
+
+
 class AstroError(RuntimeError):
     pass
 
@@ -362,6 +388,7 @@ ALL_LIBS = collections.OrderedDict(list(LIBS.items()) + list(LATER_LIBS.items())
 # __graft_entry__ look a key up in.
 OPEN_LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qduel', 'libastro_qduel.so', 'astro_qduel.hip', 'ASTRO_QDUEL_LIB', 1, 'astro_qduel_', _QDUEL_SYMBOLS),
+    _row('qpool', 'libastro_qpool.so', 'astro_qpool.hip', 'ASTRO_QPOOL_LIB', 1, 'astro_qpool_', _QPOOL_SYMBOLS),
 ))
 EVERY_LIB = collections.OrderedDict(list(ALL_LIBS.items()) + list(OPEN_LIBS.items()))
 LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
@@ -371,9 +398,10 @@ REPLAY_LIB_PATH, REPLAY_ABI_VERSION = LIBS['replay'].path, LIBS['replay'].abi
 ACTOR_LIB_PATH, ACTOR_ABI_VERSION = LIBS['actor'].path, LIBS['actor'].abi
 QOPT_LIB_PATH, QOPT_ABI_VERSION = LATER_LIBS['qopt'].path, LATER_LIBS['qopt'].abi
 QDUEL_LIB_PATH, QDUEL_ABI_VERSION = OPEN_LIBS['qduel'].path, OPEN_LIBS['qduel'].abi
+QPOOL_LIB_PATH, QPOOL_ABI_VERSION = OPEN_LIBS['qpool'].path, OPEN_LIBS['qpool'].abi
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
-_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = _qopt_lib = _qduel_lib = None
+_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = _qopt_lib = _qduel_lib = _qpool_lib = None
 
 
 def _load(key, path):
@@ -431,6 +459,7 @@ load_replay, check_replay = _public('replay')
 load_actor, check_actor = _public('actor')
 load_qopt, check_qopt = _public('qopt')
 load_qduel, check_qduel = _public('qduel')
+load_qpool, check_qpool = _public('qpool')
 
 
 def stream_ptr(device):

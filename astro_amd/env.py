@@ -36,6 +36,7 @@ from . import _lib
 from . import shard as _shard
 from .config import Bodies, State, nships as _nships
 from . import schedule as _schedule
+from .league import Pool
 
 TICK_MASK = (1 << 22) - 1
 MT_N = 624   # MT19937 state words: each env's seed stream keeps its own (stream_ring)
@@ -528,7 +529,20 @@ class BatchedEnv:
             None if explore is None else ctypes.byref(explore), float(epsilon), int(max_blocks),
             _lib.stream_ptr(self.device)), 'astro_qvalues_ships')
 
+    def _qvalues_pool(self, pool, q, control, explore, epsilon, max_blocks=0):
+        """astro_qvalues_pool (include/astro_qpool.h) on a ``league.Pool`` made for an env of this shape."""
+        if (pool.n_env, pool.S, pool.device) != (self.n_env, self.S, self.hdr.device):
+            raise ValueError('the pool was made for %d envs of %d ships on %s, this env has %d of %d on %s'
+                             % (pool.n_env, pool.S, pool.device, self.n_env, self.S, self.hdr.device))
+        _lib.check_qpool(_lib.load_qpool().astro_qvalues_pool(
+            ctypes.byref(self.params), ctypes.byref(self.state), pool._nets, len(pool._nets), pool._spans,
+            len(pool._spans), None if q is None else q.data_ptr(), None if control is None else control.data_ptr(),
+            None if explore is None else ctypes.byref(explore), float(epsilon), int(max_blocks),
+            _lib.stream_ptr(self.device)), 'astro_qvalues_pool')
+
     def _qvalues(self, net, q, control, explore, epsilon):
+        if type(net) is Pool:
+            return self._qvalues_pool(net, q, control, explore, epsilon)
         nets = self._per_ship(net)
         if nets is not None:
             return self._qvalues_ships(nets, q, control, explore, epsilon)
@@ -543,7 +557,7 @@ class BatchedEnv:
 
     def _q_buffer(self, net, out):
         nets = self._per_ship(net)
-        nout = net.nout if nets is None else [n for n in nets if n is not None][0].nout
+        nout = net.nout if nets is None else [n for n in nets if n is not None][0].nout   # (a Pool has nout too)
         shape = (self.n_env, self.S, nout)
         if out is None:
             return torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -566,7 +580,14 @@ class BatchedEnv:
         evaluated: its rows of ``out`` keep what they held (of a fresh buffer
         they are unspecified).  ValueError unless there are S entries, at
         least one network, all on the env's device, for S ships and with
-        equal nout."""
+        equal nout.
+
+        The pool form: ``net`` is a ``league.Pool`` of this env's shape --
+        ship s of the envs [lo, hi) of each of its spans is evaluated with that
+        span's network, again bit for bit what ``qvalues`` of that network
+        gives there, in one kernel (astro_qvalues_pool,
+        include/astro_qpool.h).  What no span with a network covers is treated
+        like a None ship."""
         q = self._q_buffer(net, out)
         self._qvalues(net, q, None, None, 0.0)
         return q
@@ -582,7 +603,8 @@ class BatchedEnv:
         instead of the coin: the greedy decision, then ``explore.apply(control,
         draw=tick0)``; not together with ``epsilon``.
 
-        ``net`` may be the per-ship form of ``qvalues``.  ``epsilon`` /
+        ``net`` may be the per-ship form or the pool form of ``qvalues``
+        (what a pool does not cover is a None ship's).  ``epsilon`` /
         ``explore`` apply to every ship.  A None ship's rows of ``q_out`` keep
         what they held, and its column of the returned controls is
         unspecified (the tensor comes from ``torch.empty``; ``explore`` may
@@ -621,8 +643,8 @@ class BatchedEnv:
         if opponent is None:
             nets = self._per_ship(net)
             return (net if nets is None else nets), None
-        if isinstance(net, (list, tuple)):
-            raise ValueError('opponent goes with one QNetwork, not with the per-ship form')
+        if isinstance(net, (list, tuple, Pool)):
+            raise ValueError('opponent goes with one QNetwork, not with the per-ship form or a Pool')
         if isinstance(opponent, str):
             return self._per_ship((net, None)), opponent
         return self._per_ship((net, opponent)), None
@@ -644,6 +666,8 @@ class BatchedEnv:
         net, bot = self._with_opponent(net, opponent)
         if bot is None and isinstance(net, (list, tuple)) and None in net:
             raise ValueError('every ship needs a network (or name a scripted opponent)')
+        if type(net) is Pool and not net.covered:
+            raise ValueError('every ship of every env needs a network: the pool leaves some uncovered')
         reward = torch.empty((ticks, self.n_env, self.S), dtype=torch.float32, device=self.device)
         done = torch.empty((ticks, self.n_env), dtype=torch.uint8, device=self.device)
         control = torch.empty((ticks, self.n_env, self.S), dtype=torch.int8, device=self.device)
@@ -679,6 +703,8 @@ class BatchedEnv:
         net, bot = self._with_opponent(net, opponent)
         if bot is None and isinstance(net, (list, tuple)) and None in net:
             raise ValueError('every ship needs a network (or name a scripted opponent)')
+        if type(net) is Pool and not net.covered:
+            raise ValueError('every ship of every env needs a network: the pool leaves some uncovered')
         G = int(games)
         ep = actor.Episodes(self, G)
         limit = max_ticks if max_ticks is not None else G * (self.schedule.timeout_tick + 1) + 64

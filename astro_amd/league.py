@@ -2,7 +2,14 @@
 (util.py:169-214) without scipy, and ``compare``, which plays two Q-networks
 against each other on a ``BatchedEnv`` (``play_q`` with a network opponent:
 one astro_qvalues_ships launch per tick, include/astro_qduel.h).
+
+``Pool`` describes which network plays which ship of which block of envs (one
+astro_qvalues_pool launch per tick, include/astro_qpool.h), and ``tournament``
+plays every ordered pairing of a list of networks on one env that way.
 """
+import ctypes
+
+from . import _lib
 
 
 def _tail(n, k):
@@ -67,3 +74,154 @@ def compare(env, net_a, net_b, games=1, seed=0):
     total = int(first.numel() + second.numel())
     return dict(games=total, wins_a=wins_a, wins_b=wins_b, none=total - wins_a - wins_b,
                 p_better=p_better(wins_a, wins_b))
+
+
+class Pool:
+    """Which network plays which ship of which envs: a checked, immutable
+    description that ``BatchedEnv.qvalues`` / ``qcontrols`` / ``rollout_q`` /
+    ``play_q`` take wherever they take the per-ship form (one
+    astro_qvalues_pool launch, include/astro_qpool.h).
+
+    nets: a sequence of 1..32 ``QNetwork``s on the env's device, for the env's
+    number of ships and with equal nout.  spans: a sequence of 1..64 ``(ship,
+    lo, hi, k)``: ship ``ship`` of the envs [lo, hi) is played by ``nets[k]``,
+    or by nobody when k is None (such a span, like an env no span names, is not
+    evaluated: its entries keep what they held).  0 <= lo <= hi <= n_env; the
+    spans of one ship must not overlap.  ValueError otherwise.  ``covered``:
+    every ship of every env has a network (``rollout_q`` and ``play_q`` need
+    that).  The networks' weight buffers are referenced, not copied: training
+    a network or ``copy_from`` changes what the pool plays."""
+
+    __slots__ = ('nets', 'spans', 'n_env', 'S', 'nout', 'device', 'covered', '_nets', '_spans')
+
+    def __init__(self, env, nets, spans):
+        from .qnet import QNetwork
+        nets, S, N = tuple(nets), env.S, env.n_env
+        if not 1 <= len(nets) <= _lib.QPOOL_MAX_NETS:
+            raise ValueError('a pool takes 1..%d networks, got %d' % (_lib.QPOOL_MAX_NETS, len(nets)))
+        if any(not isinstance(n, QNetwork) for n in nets):
+            raise ValueError('every network of a pool is a QNetwork')
+        for n in nets:
+            if n.weights.device != env.hdr.device:
+                raise ValueError('the network is on %s, the env on %s' % (n.weights.device, env.hdr.device))
+            if n.nships != S:
+                raise ValueError('a network for %d ships in an env of %d' % (n.nships, S))
+            if n.nout != nets[0].nout:
+                raise ValueError('the networks differ in nout (%d and %d)' % (nets[0].nout, n.nout))
+        rows = []
+        for sp in spans:
+            try:
+                ship, lo, hi, k = sp
+                bad = any(isinstance(v, bool) or v != int(v) for v in (ship, lo, hi) + (() if k is None else (k,)))
+            except (TypeError, ValueError):
+                bad = True
+            if bad:
+                raise ValueError('a span is (ship, lo, hi, k) of integers, k an index into nets or None: %r' % (sp,))
+            rows.append((int(ship), int(lo), int(hi), None if k is None else int(k)))
+        if not 1 <= len(rows) <= _lib.QPOOL_MAX_SPANS:
+            raise ValueError('a pool takes 1..%d spans, got %d' % (_lib.QPOOL_MAX_SPANS, len(rows)))
+        for ship, lo, hi, k in rows:
+            if not 0 <= ship < S:
+                raise ValueError('a span of ship %d in an env of %d ships' % (ship, S))
+            if k is not None and not 0 <= k < len(nets):
+                raise ValueError('a span of network %d in a pool of %d' % (k, len(nets)))
+            if not 0 <= lo <= hi <= N:
+                raise ValueError('a span needs 0 <= lo <= hi <= n_env (%d), got [%d, %d)' % (N, lo, hi))
+        covered = True
+        for s in range(S):
+            mine = sorted((lo, hi, k) for ship, lo, hi, k in rows if ship == s and lo < hi)
+            if any(a[1] > b[0] for a, b in zip(mine, mine[1:])):
+                raise ValueError('the spans of ship %d overlap' % s)
+            at = 0
+            for lo, hi, k in mine:
+                covered = covered and lo == at and k is not None
+                at = hi
+            covered = covered and at == N
+        self.nets, self.spans = nets, tuple(rows)
+        self.n_env, self.S, self.nout, self.device = N, S, nets[0].nout, env.hdr.device
+        self.covered = covered
+        # the C side's arrays, built once: AstroQNet is (pointer, nships, nout), and a QNetwork keeps its buffer
+        self._nets = (_lib.AstroQNet * len(nets))(*[_lib.AstroQNet(weights=n.c.weights, nships=n.nships, nout=n.nout)
+                                                    for n in nets])
+        self._spans = (_lib.AstroQSpan * len(rows))(*[_lib.AstroQSpan(ship=ship, net=-1 if k is None else k,
+                                                                      lo=lo, hi=hi) for ship, lo, hi, k in rows])
+
+    def __setattr__(self, name, value):
+        if hasattr(self, '_spans'):
+            raise AttributeError('a Pool is immutable')
+        object.__setattr__(self, name, value)
+
+    @classmethod
+    def versus(cls, env, net, rivals):
+        """``net`` as ship 0 of every env; ship 1's envs in ``len(rivals)``
+        blocks as equal as possible, block j = [j N // K, (j + 1) N // K)
+        playing ``rivals[j]``."""
+        rivals = tuple(rivals)
+        K, N = len(rivals), env.n_env
+        if env.S != 2:
+            raise ValueError('Pool.versus needs a two-ship env')
+        if not 1 <= K <= _lib.QPOOL_MAX_NETS - 1:
+            raise ValueError('Pool.versus takes 1..%d rivals, got %d' % (_lib.QPOOL_MAX_NETS - 1, K))
+        return cls(env, (net,) + rivals, [(0, 0, N, 0)] + [(1, j * N // K, (j + 1) * N // K, 1 + j) for j in range(K)])
+
+    @staticmethod
+    def pairs(m):
+        """The ordered pairs (a, b), a != b, of range(m) in lexicographic order."""
+        return [(a, b) for a in range(m) for b in range(m) if a != b]
+
+    @classmethod
+    def pairings(cls, env, nets):
+        """One block of envs per ordered pair (a, b), a != b, of ``nets`` in
+        lexicographic order: block j of P = M (M - 1) is [j N // P, (j + 1) N
+        // P), ship 0 played by ``nets[a]`` and ship 1 by ``nets[b]``.  Needs a
+        two-ship env, M >= 2, 2 P <= 64 spans (M <= 6) and N >= P."""
+        nets = tuple(nets)
+        pairs, N = cls.pairs(len(nets)), env.n_env
+        P = len(pairs)
+        if env.S != 2:
+            raise ValueError('Pool.pairings needs a two-ship env')
+        if P < 2 or 2 * P > _lib.QPOOL_MAX_SPANS:
+            raise ValueError('Pool.pairings takes 2..6 networks (two spans per ordered pair, at most %d), got %d'
+                             % (_lib.QPOOL_MAX_SPANS, len(nets)))
+        if N < P:
+            raise ValueError('Pool.pairings of %d networks needs at least %d envs, got %d' % (len(nets), P, N))
+        spans = []
+        for j, (a, b) in enumerate(pairs):
+            lo, hi = j * N // P, (j + 1) * N // P
+            spans += [(0, lo, hi, a), (1, lo, hi, b)]
+        return cls(env, nets, spans)
+
+
+def tournament(env, nets, games=1, seed=0):
+    """Every network of ``nets`` against every other on ``env`` (two ships,
+    auto-reset) in one ``play_q`` loop on ``Pool.pairings(env, nets)``: the envs
+    of block (a, b) play their next ``games`` games with ``nets[a]`` as ship 0
+    and ``nets[b]`` as ship 1, all greedy.  Returns ``dict(games=, wins=, none=,
+    p_better=)`` of M x M nested lists: ``wins[a][b]`` a's wins over b over both
+    seats, ``games[a][b]`` the games the two played (symmetric, as is
+    ``none[a][b]``, those without a winner), ``p_better[a][b] =
+    p_better(wins[a][b], wins[b][a])``; the diagonal is 0 / 0.5.  The counts
+    are taken on the device and read once at the end."""
+    import torch
+    nets = tuple(nets)
+    pool = Pool.pairings(env, nets)
+    winner = env._play_q(pool, None, games, None, None, seed).winner      # int8 [N, G]: -1 none, 0, 1
+    M, N, pairs = len(nets), env.n_env, Pool.pairs(len(nets))
+    P = len(pairs)
+    block = torch.tensor([j for j in range(P) for _ in range((j + 1) * N // P - j * N // P)], dtype=torch.int64,
+                         device=winner.device)
+    slot = block[:, None] * 3 + (winner.to(torch.int64) + 1)            # per block: none, ship 0 won, ship 1 won
+    counts = torch.zeros(3 * P, dtype=torch.int64, device=winner.device)
+    counts.scatter_add_(0, slot.reshape(-1), torch.ones(slot.numel(), dtype=torch.int64, device=winner.device))
+    counts = counts.cpu().view(P, 3).tolist()
+    wins = [[0] * M for _ in range(M)]
+    none = [[0] * M for _ in range(M)]
+    played = [[0] * M for _ in range(M)]
+    for (a, b), (n_none, n0, n1) in zip(pairs, counts):
+        wins[a][b] += n0
+        wins[b][a] += n1
+        for x, y in ((a, b), (b, a)):
+            none[x][y] += n_none
+            played[x][y] += n_none + n0 + n1
+    return dict(games=played, wins=wins, none=none,
+                p_better=[[p_better(wins[a][b], wins[b][a]) for b in range(M)] for a in range(M)])

@@ -42,10 +42,17 @@ class QTrainer:
     ``net.clone()``, refreshed with ``rival.copy_from(net)`` after every K-th
     optimisation step -- self-play against a frozen copy of oneself.  With a
     network as ship 1 ``explore`` applies to both ships, and both ships'
-    experiences go to the ring as before."""
+    experiences go to the ring as before.  opponent='pool' with pool_size=K
+    (1..31) and opponent_sync=J: ``self.rivals`` is K clones of ``net``, ship 1
+    of the j-th of K blocks of envs plays ``rivals[j]`` (``league.Pool.versus``,
+    astro_qpool.h: still one acting launch per tick), and after every J-th
+    optimisation step the oldest slot is refreshed with ``copy_from(net)``,
+    round robin from slot 0 -- self-play against copies of oneself of K
+    different ages.  pool_size=1 is 'snapshot' bit for bit.  pool_size goes with
+    'pool' only."""
 
     def __init__(self, env, net, buf, explore, n_samples=1024, n_ministeps=1, lr=1e-2, seed=0,
-                 optimizer=None, target_sync=None, double=False, opponent=None, opponent_sync=None):
+                 optimizer=None, target_sync=None, double=False, opponent=None, opponent_sync=None, pool_size=None):
         if buf.n_env != env.n_env or buf.nships != env.S:
             raise ValueError('the replay buffer is [%d envs, %d ships], the env [%d, %d]'
                              % (buf.n_env, buf.nships, env.n_env, env.S))
@@ -65,22 +72,35 @@ class QTrainer:
             else:
                 raise ValueError('target_sync must be an int >= 1 (steps between hard copies) or a float in (0, 1)')
             self.target = net.clone()
-        self.rival, self.rival_every = None, None
-        if isinstance(opponent, str) and opponent == 'snapshot':
+        self.rival, self.rival_every, self.rivals = None, None, None
+        pool = isinstance(opponent, str) and opponent == 'pool'
+        if pool_size is not None and not pool:
+            raise ValueError("pool_size goes with opponent='pool' only")
+        if pool or (isinstance(opponent, str) and opponent == 'snapshot'):
             if not (isinstance(opponent_sync, int) and not isinstance(opponent_sync, bool) and opponent_sync >= 1):
-                raise ValueError("opponent='snapshot' needs opponent_sync, an int >= 1 (optimisation steps "
-                                 'between refreshes)')
+                raise ValueError('opponent=%r needs opponent_sync, an int >= 1 (optimisation steps '
+                                 'between refreshes)' % opponent)
+            if pool and not (isinstance(pool_size, int) and not isinstance(pool_size, bool) and 1 <= pool_size <= 31):
+                raise ValueError("opponent='pool' needs pool_size, an int in [1, 31]")
             if env.S != 2:
                 raise ValueError('opponent needs a two-ship env')
-            self.rival, self.rival_every = net.clone(), opponent_sync
+            self.rival_every = opponent_sync
+            if pool:
+                self.rivals = [net.clone() for _ in range(pool_size)]
+            else:
+                self.rival = net.clone()
         else:
             if opponent_sync is not None:
-                raise ValueError("opponent_sync goes with opponent='snapshot' only")
+                raise ValueError("opponent_sync goes with opponent='snapshot' or 'pool' only")
             env._check_opponent(opponent)
             if opponent is not None and not isinstance(opponent, str):
                 self.rival = opponent
         # what env.qcontrols takes, and the scripted name whose controls fill ship 1's column
-        self._acting, self._bot = env._with_opponent(net, opponent if self.rival is None else self.rival)
+        if pool:
+            from .league import Pool
+            self._acting, self._bot = Pool.versus(env, net, self.rivals), None
+        else:
+            self._acting, self._bot = env._with_opponent(net, opponent if self.rival is None else self.rival)
 
     def _targets(self, r, d, nf, term):
         valuer = self.net if self.target is None else self.target
@@ -118,7 +138,10 @@ class QTrainer:
             buf.update_loss(ids, loss)
             self.nstep += 1
             if self.rival_every is not None and self.nstep % self.rival_every == 0:
-                self.rival.copy_from(net)
+                if self.rivals is None:
+                    self.rival.copy_from(net)
+                else:   # the oldest slot: round robin from slot 0
+                    self.rivals[(self.nstep // self.rival_every - 1) % len(self.rivals)].copy_from(net)
             out = dict(loss=loss.sum(), n=torch.full((), ids.shape[0], dtype=torch.int32, device=loss.device))
         self.last = out
         return out

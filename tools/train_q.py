@@ -13,7 +13,10 @@ seeds before every validation, so every point of the curve plays the same
 games.  --optimizer, --target-sync, --double, --opponent, --max-norm and
 --weight-decay select QTrainer's options (astro_amd.optim); without them the
 run is the one described above.  --opponent snapshot --opponent-sync K trains
-against a frozen copy of the network, refreshed every K optimisation steps.  The
+against a frozen copy of the network, refreshed every K optimisation steps;
+--opponent pool --pool-size M against M such copies of different ages, each
+playing ship 1 of a block of the envs, the oldest refreshed every K steps.
+--tournament M adds league.tournament over M of the validations' networks.  The
 settings are part of the arguments the curve file records.
 
 Writes one JSON document to --out: the arguments, and per validation the tick,
@@ -55,10 +58,16 @@ def main():
     ap.add_argument('--target-sync', default=None,
                     help='an integer K: a target network hard-copied every K steps; a float in (0, 1): Polyak tau')
     ap.add_argument('--double', action='store_true', help='Double-DQN targets')
-    ap.add_argument('--opponent', choices=('script', 'nothing', 'random', 'snapshot'), default=None,
+    ap.add_argument('--opponent', choices=('script', 'nothing', 'random', 'snapshot', 'pool'), default=None,
                     help='ship 1 of the training envs plays this bot instead of the network; snapshot: a frozen copy '
-                         'of the network, refreshed every --opponent-sync optimisation steps')
-    ap.add_argument('--opponent-sync', type=int, default=None, help='with --opponent snapshot: steps between refreshes')
+                         'of the network, refreshed every --opponent-sync optimisation steps; pool: --pool-size such '
+                         'copies, each playing a block of the envs, the oldest refreshed every --opponent-sync steps')
+    ap.add_argument('--opponent-sync', type=int, default=None,
+                    help='with --opponent snapshot / pool: steps between refreshes')
+    ap.add_argument('--pool-size', type=int, default=None, help='with --opponent pool: the number of frozen copies')
+    ap.add_argument('--tournament', type=int, default=0,
+                    help='M in 2..6: after the run, league.tournament over M of the validations\' networks (evenly '
+                         'spaced, first and last included) on a fresh evaluation env; recorded as "tournament"')
     ap.add_argument('--max-norm', type=float, default=None, help='clip the gradient norm to this')
     ap.add_argument('--weight-decay', type=float, default=0.0)
     args = ap.parse_args()
@@ -80,7 +89,9 @@ def main():
                'rmsprop': lambda: optim.RMSprop(**common), 'adagrad': lambda: optim.Adagrad(**common),
                'adam': lambda: optim.Adam(**common)}[args.optimizer]()
     tr = train.QTrainer(env, net, buf, eg, n_samples=args.n_samples, lr=args.lr, seed=args.seed, optimizer=opt,
-                        target_sync=sync, double=args.double, opponent=args.opponent, opponent_sync=args.opponent_sync)
+                        target_sync=sync, double=args.double, opponent=args.opponent, opponent_sync=args.opponent_sync,
+                        pool_size=args.pool_size)
+    checkpoints = []                               # (tick, the network then), one per validation
     eval_cfg = DEFAULT_CONFIG._replace(max_time=args.max_time)
     curve = []
     t0 = time.time()
@@ -104,6 +115,8 @@ def main():
         if tick:
             point['vs_previous'], point['vs_first'] = against(previous), against(first)
             previous.copy_from(net)
+        if args.tournament:
+            checkpoints.append((tick, net.clone()))
         curve.append(point)
         print(json.dumps(point), flush=True)
 
@@ -114,6 +127,15 @@ def main():
     env.check_errors()
     doc = dict(args=vars(args), device=torch.cuda.get_device_name(0), train_seconds=round(time.time() - t0, 2),
                curve=curve)
+    if args.tournament:
+        M = min(args.tournament, len(checkpoints))
+        picked = [checkpoints[round(k * (len(checkpoints) - 1) / (M - 1))] for k in range(M)]
+        ev = BatchedEnv(eval_cfg, args.eval_envs, device=dev, b_cap=32, env_offset=1 << 20)
+        ev.reset()
+        doc['tournament'] = dict(ticks=[t for t, _ in picked],
+                                 **league.tournament(ev, [n for _, n in picked], games=args.games))
+        ev.check_errors()
+        print(json.dumps(doc['tournament']), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(doc, f, indent=1)
