@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 CFG = gio.configs()
 DEV = 'cuda:0'
 F32, F64 = torch.float32, torch.float64
-# csrc/astro_qnet.hip: MAX_BLOCKS workgroups of QN_WAVES waves, SEGS (env, ego) segments per chunk
+# csrc/astro_qfwd.h: MAX_BLOCKS workgroups of QN_WAVES waves, SEGS (env, ego) segments per chunk
 MAX_BLOCKS, QN_WAVES, SEGS = 512, 4, 32
 
 

@@ -62,11 +62,18 @@ def test_the_table_row():
     assert (L.version, L.error, L.handle) == ('astro_qpool_abi_version', 'astro_qpool_last_error', '_qpool_lib')
     assert _lib.EVERY_LIB['qpool'] is L and _lib.QPOOL_LIB_PATH is L.path and _lib._QPOOL_SYMBOLS is L.symbols
     assert callable(_lib.load_qpool) and callable(_lib.check_qpool)
-    deps = entry.dependencies(os.path.join(ROOT, 'astro_amd', 'csrc', L.source))
+    csrc = os.path.join(ROOT, 'astro_amd', 'csrc')
+    deps = entry.dependencies(os.path.join(csrc, L.source))
     assert {os.path.basename(d) for d in deps} == {'astro_qpool.hip', 'astro_qpool.h', 'astro_qnet.h', 'astro_step.h',
-                                                  'astro_common.h'}
-    assert sorted(f for f in os.listdir(os.path.join(ROOT, 'astro_amd', 'csrc')) if f.endswith('.h')) \
-        == ['astro_common.h']
+                                                  'astro_common.h', 'astro_qfwd.h'}
+    deps = entry.dependencies(os.path.join(csrc, 'astro_qnet.hip'))
+    assert {os.path.basename(d) for d in deps} == {'astro_qnet.hip', 'astro_qnet.h', 'astro_step.h', 'astro_common.h',
+                                                  'astro_qfwd.h'}
+    assert sorted(f for f in os.listdir(csrc) if f.endswith('.h')) == ['astro_common.h', 'astro_qfwd.h']
+    # the forward's helpers are astro_qfwd.h's: no Q-network source states them again
+    for name in ('astro_qnet.hip', 'astro_qduel.hip', L.source):
+        text = open(os.path.join(csrc, name)).read()
+        assert not re.search(r'\bfloat\s+softsign\b|\bstruct\s+WaveLds\b|\bstruct\s+Explore\b', text), name
     entry.build()
     assert os.path.exists(L.path)
 
