@@ -8,7 +8,9 @@ exposes the reference's single-game create/step/play surface on top of it;
 bookkeeping, ``QTrainer`` (train.py) the training loop made of them, ``SGD``,
 ``RMSprop``, ``Adagrad`` and ``Adam`` (optim.py) its update rules, ``league``
 (league.py) the comparison of networks: ``p_better``, ``find_better``,
-``compare``, and ``Pool`` / ``tournament`` for many networks on one env.
+``compare``, and ``Pool`` / ``tournament`` for many networks on one env,
+``Recorder`` (record.py) whole games of chosen envs recorded on the device, as
+the reference's ``Game`` / ``Tick`` logs with the networks' Q values.
 """
 from .config import (Bodies, Config, DEFAULT_CONFIG, Game, SOLO_CONFIG,  # noqa: F401
                      SOLO_EASY_CONFIG, State, Tick, generate_configs)
@@ -19,3 +21,5 @@ from .optim import SGD, Adagrad, Adam, RMSprop  # noqa: F401
 from .train import QTrainer  # noqa: F401
 from . import league  # noqa: F401
 from .league import Pool, compare, find_better, p_better, tournament  # noqa: F401
+from . import record  # noqa: F401
+from .record import Recorder  # noqa: F401

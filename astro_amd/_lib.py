@@ -2,8 +2,9 @@
 libastro_qnet.so (include/astro_qnet.h), of libastro_qtrain.so
 (include/astro_qtrain.h), of libastro_replay.so (include/astro_replay.h), of
 libastro_actor.so (include/astro_actor.h), of libastro_qopt.so
-(include/astro_qopt.h), of libastro_qduel.so (include/astro_qduel.h) and of
-libastro_qpool.so (include/astro_qpool.h).
+(include/astro_qopt.h), of libastro_qduel.so (include/astro_qduel.h), of
+libastro_qpool.so (include/astro_qpool.h) and of libastro_trace.so
+(include/astro_trace.h).
 
 The shared library is built in-tree by ``__graft_entry__.build()``
 (hipcc --offload-arch=gfx950).  There is no fallback: if the library is
@@ -350,6 +351,40 @@ _QPOOL_SYMBOLS = {
 }
 
 
+class AstroTrace(ctypes.Structure):
+    """include/astro_trace.h AstroTrace: the trace ring's arrays and shape."""
+    _fields_ = [
+        ('ids', ctypes.c_void_p),
+        ('ships', ctypes.c_void_p),
+        ('ships_b', ctypes.c_void_p),
+        ('planets', ctypes.c_void_p),
+        ('bullets', ctypes.c_void_p),
+        ('hdr', ctypes.c_void_p),
+        ('control', ctypes.c_void_p),
+        ('q', ctypes.c_void_p),
+        ('reward', ctypes.c_void_p),
+        ('done', ctypes.c_void_p),
+        ('m', ctypes.c_int32),
+        ('ticks', ctypes.c_int32),
+        ('nout', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+    ]
+
+
+TRACE_MAX_OUT = 6       # include/astro_trace.h ASTRO_TRACE_MAX_OUT
+
+# libastro_trace.so: whole games of chosen envs recorded on the device, a library of its own (include/astro_trace.h)
+_TRACE_SYMBOLS = {
+    'astro_trace_abi_version': (ctypes.c_int, []),
+    'astro_trace_last_error': (ctypes.c_char_p, []),
+    'astro_trace_state': (ctypes.c_int, [ctypes.POINTER(AstroParams), ctypes.POINTER(AstroState),
+                                         ctypes.POINTER(AstroTrace), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    'astro_trace_result': (ctypes.c_int, [ctypes.POINTER(AstroTrace), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+}
+
+
 class AstroError(RuntimeError):
     pass
 
@@ -389,6 +424,7 @@ ALL_LIBS = collections.OrderedDict(list(LIBS.items()) + list(LATER_LIBS.items())
 OPEN_LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qduel', 'libastro_qduel.so', 'astro_qduel.hip', 'ASTRO_QDUEL_LIB', 1, 'astro_qduel_', _QDUEL_SYMBOLS),
     _row('qpool', 'libastro_qpool.so', 'astro_qpool.hip', 'ASTRO_QPOOL_LIB', 1, 'astro_qpool_', _QPOOL_SYMBOLS),
+    _row('trace', 'libastro_trace.so', 'astro_trace.hip', 'ASTRO_TRACE_LIB', 1, 'astro_trace_', _TRACE_SYMBOLS),
 ))
 EVERY_LIB = collections.OrderedDict(list(ALL_LIBS.items()) + list(OPEN_LIBS.items()))
 LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
@@ -399,9 +435,11 @@ ACTOR_LIB_PATH, ACTOR_ABI_VERSION = LIBS['actor'].path, LIBS['actor'].abi
 QOPT_LIB_PATH, QOPT_ABI_VERSION = LATER_LIBS['qopt'].path, LATER_LIBS['qopt'].abi
 QDUEL_LIB_PATH, QDUEL_ABI_VERSION = OPEN_LIBS['qduel'].path, OPEN_LIBS['qduel'].abi
 QPOOL_LIB_PATH, QPOOL_ABI_VERSION = OPEN_LIBS['qpool'].path, OPEN_LIBS['qpool'].abi
+TRACE_LIB_PATH, TRACE_ABI_VERSION = OPEN_LIBS['trace'].path, OPEN_LIBS['trace'].abi
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
 _lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = _qopt_lib = _qduel_lib = _qpool_lib = None
+_trace_lib = None
 
 
 def _load(key, path):
@@ -460,6 +498,7 @@ load_actor, check_actor = _public('actor')
 load_qopt, check_qopt = _public('qopt')
 load_qduel, check_qduel = _public('qduel')
 load_qpool, check_qpool = _public('qpool')
+load_trace, check_trace = _public('trace')
 
 
 def stream_ptr(device):

@@ -60,3 +60,27 @@ def generate_configs_filtered(config, planets):
 
 def nships(config):
     return 1 if config.solo else 2
+
+
+def reference_state(ships, ships_b, planets, bullets, tick, schedule):
+    """The reference-shaped State of one env's rows (``BatchedEnv.state_of`` and
+    ``record.decode``): ships [S, 4], ships_b [S], the live planets [nplanets,
+    4] and the live bullets [nbullets, 4] of any float dtype, the env's tick
+    counter and the config's ``schedule.Schedule``.  Reference dtypes: float32
+    arrays for a fresh game (tick 0), float64 after its first step; a
+    one-planet game's planets stay float32 (core.py:119-124, 185-193);
+    ``reload`` and ``t`` come from the schedule."""
+    tick, npl = int(tick), int(planets.shape[0])
+    fresh = tick == 0
+    f = np.float32 if fresh else np.float64
+    ships = ships.astype(np.float64)
+    pl = planets.astype(np.float64)
+    bl = bullets.astype(np.float64)
+    pf = np.float32 if (fresh or npl == 1) else np.float64
+    pdxf = np.float32 if npl == 1 else np.float64
+    k = min(tick, schedule.timeout_tick)
+    return State(
+        ships=Bodies(x=ships[:, 0:2].astype(f), dx=ships[:, 2:4].astype(f), b=ships_b.astype(f)),
+        planets=Bodies(x=pl[:, 0:2].astype(pf), dx=pl[:, 2:4].astype(pdxf), b=None),
+        bullets=Bodies(x=bl[:, 0:2].astype(f), dx=bl[:, 2:4].astype(f), b=None),
+        reload=float(schedule.reload[k]), t=float(schedule.t[k]))

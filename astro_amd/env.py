@@ -34,7 +34,7 @@ import torch
 
 from . import _lib
 from . import shard as _shard
-from .config import Bodies, State, nships as _nships
+from .config import nships as _nships, reference_state as _reference_state
 from . import schedule as _schedule
 from .league import Pool
 
@@ -681,7 +681,7 @@ class BatchedEnv:
             done[t] = d
         return reward, done, control
 
-    def play_q(self, net, opponent=None, games=1, explore=None, max_ticks=None, seed=0):
+    def play_q(self, net, opponent=None, games=1, explore=None, max_ticks=None, seed=0, record=None):
         """``play`` with the network deciding: every env plays its next
         ``games`` games (auto-reset onto its generate_configs stream) from its
         current state, ``net`` greedy for every ship (rl.train's validation,
@@ -693,11 +693,16 @@ class BatchedEnv:
         ships' with a network opponent).  A host
         loop of ``qcontrols``, ``step`` and ``actor.Episodes.push`` per tick;
         the device count of finished games is read every 64 ticks only.
+        record: a ``record.Recorder`` of this env with at least 64 slots -- its
+        envs' ticks are recorded on the device (state, controls, the networks'
+        Q values as ``bot_data``, reward; two more launches per tick) and
+        drained where the loop synchronises anyway; the games end up in
+        ``record.games``.  Without it the call makes the launches it always made.
         Returns ``play``'s (winner int64 [N, games], length int64 [N, games])."""
-        ep = self._play_q(net, opponent, games, explore, max_ticks, seed)
+        ep = self._play_q(net, opponent, games, explore, max_ticks, seed, record)
         return ep.winner.to(torch.int64), ep.ticks.to(torch.int64)
 
-    def _play_q(self, net, opponent, games, explore, max_ticks, seed):
+    def _play_q(self, net, opponent, games, explore, max_ticks, seed, record=None):
         """play_q's loop; returns its ``actor.Episodes``."""
         from . import actor
         net, bot = self._with_opponent(net, opponent)
@@ -705,6 +710,16 @@ class BatchedEnv:
             raise ValueError('every ship needs a network (or name a scripted opponent)')
         if type(net) is Pool and not net.covered:
             raise ValueError('every ship of every env needs a network: the pool leaves some uncovered')
+        q_out = played = None
+        if record is not None:
+            if getattr(record, 'env', None) is not self:
+                raise ValueError('record must be a Recorder of this env')
+            if record.ticks < 64:
+                raise ValueError('play_q drains the recorder every 64 ticks: it needs ticks >= 64, got %d'
+                                 % record.ticks)
+            if record.wants_q:   # a scripted opponent's ship has no network: its rows stay zero and are not reported
+                q_out = torch.zeros(self._q_buffer(net, None).shape, dtype=torch.float32, device=self.device)
+                played = [True] * self.S if bot is None else [True, False]
         G = int(games)
         ep = actor.Episodes(self, G)
         limit = max_ticks if max_ticks is not None else G * (self.schedule.timeout_tick + 1) + 64
@@ -713,12 +728,18 @@ class BatchedEnv:
             if t >= limit:
                 raise RuntimeError('play_q: games did not finish within %d ticks' % limit)
             for _ in range(64):
-                c = self.qcontrols(net, tick0=t, explore=explore)
+                c = self.qcontrols(net, tick0=t, explore=explore, q_out=q_out)
                 if bot is not None:
                     c[:, 1] = self.controls(bot, seed, t)[:, 1]
+                if record is not None:
+                    record.state(c, q_out, played)
                 _, r, d = self.step(c, auto_reset=True)
+                if record is not None:
+                    record.result(r, d)
                 ep.push(r, d)
                 t += 1
+            if record is not None:
+                record.drain()
             if int(ep.got.min()) >= G:
                 break
         return ep
@@ -774,21 +795,7 @@ class BatchedEnv:
         """Reference-shaped State of env i (numpy, reference dtypes: float32
         arrays for a fresh game, float64 after its first step)."""
         h = host or self.to_host()
-        tick = int(h['tick'][i])
         npl = int(h['nplanets'][i])
         nb = int(h['nbullets'][i])
-        fresh = tick == 0
-        f = np.float32 if fresh else np.float64
-        ships = h['ships'][i].astype(np.float64)
-        pl = h['planets'][i, :npl].astype(np.float64)
-        bl = h['bullets'][i, :nb].astype(np.float64)
-        pf = np.float32 if (fresh or npl == 1) else np.float64
-        pdxf = np.float32 if npl == 1 else np.float64
-        sch = self.schedule
-        k = min(tick, sch.timeout_tick)
-        return State(
-            ships=Bodies(x=ships[:, 0:2].astype(f), dx=ships[:, 2:4].astype(f),
-                         b=h['ships_b'][i].astype(f)),
-            planets=Bodies(x=pl[:, 0:2].astype(pf), dx=pl[:, 2:4].astype(pdxf), b=None),
-            bullets=Bodies(x=bl[:, 0:2].astype(f), dx=bl[:, 2:4].astype(f), b=None),
-            reload=float(sch.reload[k]), t=float(sch.t[k]))
+        return _reference_state(h['ships'][i], h['ships_b'][i], h['planets'][i, :npl], h['bullets'][i, :nb],
+                                h['tick'][i], self.schedule)

@@ -153,11 +153,14 @@ class QTrainer:
             out = self.tick()
         return out
 
-    def validate(self, eval_env, games=1, opponent=None):
+    def validate(self, eval_env, games=1, opponent=None, record=None):
         """rl.train's validation (rl.py:352-369): ``eval_env.play_q(net,
         opponent, games)`` with the greedy network from the env's current
         states, as ``actor.Episodes.summary()`` -- the share of games won by
         each ship (ship 0 is the network), the share without a winner and the
         median length in ticks.  opponent: None, a scripted bot's name or a
-        ``QNetwork`` (``self.rival``, say) as ship 1.  Synchronises."""
-        return eval_env._play_q(self.net, opponent, games, None, None, 0).summary()
+        ``QNetwork`` (``self.rival``, say) as ship 1.  record: a
+        ``record.Recorder`` of ``eval_env`` (see ``play_q``): the games of its
+        envs, with the network's Q values, as rl.train saves its validation
+        game (rl.py:354-355).  Synchronises."""
+        return eval_env._play_q(self.net, opponent, games, None, None, 0, record).summary()

@@ -17,7 +17,11 @@ against a frozen copy of the network, refreshed every K optimisation steps;
 --opponent pool --pool-size M against M such copies of different ages, each
 playing ship 1 of a block of the envs, the oldest refreshed every K steps.
 --tournament M adds league.tournament over M of the validations' networks.  The
-settings are part of the arguments the curve file records.
+settings are part of the arguments the curve file records.  --log-dir DIR saves
+the validation games against ScriptBot of the first --log-envs evaluation envs,
+recorded on the device with the network's Q values (astro_amd.record), as
+DIR/<tick>/<env>_<k>.log in the reference's log format -- what rl.train saves
+at each validation (rl.py:354-355), for the reference's viewer.
 
 Writes one JSON document to --out: the arguments, and per validation the tick,
 the optimisation steps so far, the last loss per sample, both summaries and,
@@ -35,7 +39,8 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
-from astro_amd import BatchedEnv, DEFAULT_CONFIG, ReplayBuffer, actor, league, optim, qnet, train  # noqa: E402
+from astro_amd import (BatchedEnv, DEFAULT_CONFIG, ReplayBuffer, actor, league, optim, qnet, record,  # noqa: E402
+                       train)
 
 
 def main():
@@ -70,6 +75,9 @@ def main():
                          'spaced, first and last included) on a fresh evaluation env; recorded as "tournament"')
     ap.add_argument('--max-norm', type=float, default=None, help='clip the gradient norm to this')
     ap.add_argument('--weight-decay', type=float, default=0.0)
+    ap.add_argument('--log-dir', default=None,
+                    help='save the recorded validation games against ScriptBot as DIR/<tick>/<env>_<k>.log')
+    ap.add_argument('--log-envs', type=int, default=4, help='with --log-dir: the evaluation envs 0 .. n-1 are recorded')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'train_q needs a HIP device'
     dev = 'cuda:0'
@@ -111,7 +119,12 @@ def main():
         for opponent in ('nothing', 'script'):
             ev = BatchedEnv(eval_cfg, args.eval_envs, device=dev, b_cap=32, env_offset=1 << 20)
             ev.reset()
-            point[opponent] = tr.validate(ev, games=args.games, opponent=opponent)
+            rec = None
+            if args.log_dir and opponent == 'script':
+                rec = record.Recorder(ev, range(min(args.log_envs, args.eval_envs)), q=True, limit=args.games)
+            point[opponent] = tr.validate(ev, games=args.games, opponent=opponent, record=rec)
+            if rec is not None:
+                point['logs'] = len(rec.save(os.path.join(args.log_dir, str(tick))))
         if tick:
             point['vs_previous'], point['vs_first'] = against(previous), against(first)
             previous.copy_from(net)
