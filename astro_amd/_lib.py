@@ -1,14 +1,20 @@
-"""ctypes binding of libastro_hip.so (include/astro_step.h), of
-libastro_qnet.so (include/astro_qnet.h), of libastro_qtrain.so
-(include/astro_qtrain.h), of libastro_replay.so (include/astro_replay.h), of
-libastro_actor.so (include/astro_actor.h), of libastro_qopt.so
-(include/astro_qopt.h), of libastro_qduel.so (include/astro_qduel.h), of
-libastro_qpool.so (include/astro_qpool.h) and of libastro_trace.so
-(include/astro_trace.h).
+"""ctypes binding of the project's shared libraries, one row of ``LIBS`` each:
 
-The shared library is built in-tree by ``__graft_entry__.build()``
-(hipcc --offload-arch=gfx950).  There is no fallback: if the library is
-missing or its ABI version differs, every entry point raises.
+    key     library              header (include/)
+    hip     libastro_hip.so      astro_step.h
+    qnet    libastro_qnet.so     astro_qnet.h
+    qtrain  libastro_qtrain.so   astro_qtrain.h
+    replay  libastro_replay.so   astro_replay.h
+    actor   libastro_actor.so    astro_actor.h
+    qopt    libastro_qopt.so     astro_qopt.h
+    qduel   libastro_qduel.so    astro_qduel.h
+    qpool   libastro_qpool.so    astro_qpool.h
+    trace   libastro_trace.so    astro_trace.h
+
+The libraries are built in-tree by ``__graft_entry__.build()`` (hipcc
+--offload-arch=gfx950).  There is no fallback: if a library is missing or its
+ABI version differs, every entry point of it raises.  tests/test_libraries.py
+checks every row against its header and its built library.
 """
 import collections
 import ctypes
@@ -407,45 +413,30 @@ LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qtrain', 'libastro_qtrain.so', 'astro_qtrain.hip', 'ASTRO_QTRAIN_LIB', 1, 'astro_qtrain_', _QTRAIN_SYMBOLS),
     _row('replay', 'libastro_replay.so', 'astro_replay.hip', 'ASTRO_REPLAY_LIB', 1, 'astro_replay_', _REPLAY_SYMBOLS),
     _row('actor', 'libastro_actor.so', 'astro_actor.hip', 'ASTRO_ACTOR_LIB', 1, 'astro_actor_', _ACTOR_SYMBOLS),
-))
-# Why two tables: LIBS is the five libraries whose symbol tables, ABI numbers
-# and very keys the host tests pin; a library that came after them is a row of
-# LATER_LIBS, made by the same _row and built, loaded and checked by the same
-# code.
-LATER_LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qopt', 'libastro_qopt.so', 'astro_qopt.hip', 'ASTRO_QOPT_LIB', 1, 'astro_qopt_', _QOPT_SYMBOLS),
-))
-ALL_LIBS = collections.OrderedDict(list(LIBS.items()) + list(LATER_LIBS.items()))
-# The third table is the open-ended one: the host tests pin LATER_LIBS and
-# ALL_LIBS to what they were when they were written as well, so every library
-# from here on is a row of OPEN_LIBS, and no test may pin ITS key set.
-# EVERY_LIB (LIBS, LATER_LIBS, OPEN_LIBS) is what the code below and
-# __graft_entry__ look a key up in.
-OPEN_LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qduel', 'libastro_qduel.so', 'astro_qduel.hip', 'ASTRO_QDUEL_LIB', 1, 'astro_qduel_', _QDUEL_SYMBOLS),
     _row('qpool', 'libastro_qpool.so', 'astro_qpool.hip', 'ASTRO_QPOOL_LIB', 1, 'astro_qpool_', _QPOOL_SYMBOLS),
     _row('trace', 'libastro_trace.so', 'astro_trace.hip', 'ASTRO_TRACE_LIB', 1, 'astro_trace_', _TRACE_SYMBOLS),
 ))
-EVERY_LIB = collections.OrderedDict(list(ALL_LIBS.items()) + list(OPEN_LIBS.items()))
 LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
 QNET_LIB_PATH, QNET_ABI_VERSION = LIBS['qnet'].path, LIBS['qnet'].abi
 QTRAIN_LIB_PATH, QTRAIN_ABI_VERSION = LIBS['qtrain'].path, LIBS['qtrain'].abi
 REPLAY_LIB_PATH, REPLAY_ABI_VERSION = LIBS['replay'].path, LIBS['replay'].abi
 ACTOR_LIB_PATH, ACTOR_ABI_VERSION = LIBS['actor'].path, LIBS['actor'].abi
-QOPT_LIB_PATH, QOPT_ABI_VERSION = LATER_LIBS['qopt'].path, LATER_LIBS['qopt'].abi
-QDUEL_LIB_PATH, QDUEL_ABI_VERSION = OPEN_LIBS['qduel'].path, OPEN_LIBS['qduel'].abi
-QPOOL_LIB_PATH, QPOOL_ABI_VERSION = OPEN_LIBS['qpool'].path, OPEN_LIBS['qpool'].abi
-TRACE_LIB_PATH, TRACE_ABI_VERSION = OPEN_LIBS['trace'].path, OPEN_LIBS['trace'].abi
+QOPT_LIB_PATH, QOPT_ABI_VERSION = LIBS['qopt'].path, LIBS['qopt'].abi
+QDUEL_LIB_PATH, QDUEL_ABI_VERSION = LIBS['qduel'].path, LIBS['qduel'].abi
+QPOOL_LIB_PATH, QPOOL_ABI_VERSION = LIBS['qpool'].path, LIBS['qpool'].abi
+TRACE_LIB_PATH, TRACE_ABI_VERSION = LIBS['trace'].path, LIBS['trace'].abi
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
-_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = _qopt_lib = _qduel_lib = _qpool_lib = None
-_trace_lib = None
+_lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = None
+_qopt_lib = _qduel_lib = _qpool_lib = _trace_lib = None
 
 
 def _load(key, path):
-    """The library of EVERY_LIB[key], loaded from `path` and typed on the first call.  Raises if
+    """The library of LIBS[key], loaded from `path` and typed on the first call.  Raises if
     it is absent or stale."""
-    L = EVERY_LIB[key]
+    L = LIBS[key]
     lib = globals()[L.handle]
     if lib is not None:
         return lib
@@ -472,15 +463,15 @@ def _load(key, path):
 
 def _check(key, rc, what):
     """Raise the library's last error for the entry point `what` that returned rc != 0."""
-    msg = getattr(_load(key, EVERY_LIB[key].path), EVERY_LIB[key].error)().decode(errors='replace')
+    msg = getattr(_load(key, LIBS[key].path), LIBS[key].error)().decode(errors='replace')
     raise AstroError('%s failed (%d): %s' % (what, rc, msg))
 
 
 def _public(key):
     """The library's public pair; what a call per step pays is one lookup and one compare."""
-    loaded, handle = globals(), EVERY_LIB[key].handle
+    loaded, handle = globals(), LIBS[key].handle
 
-    def load(path=EVERY_LIB[key].path):
+    def load(path=LIBS[key].path):
         lib = loaded[handle]
         return lib if lib is not None else _load(key, path)
 

@@ -1,14 +1,9 @@
 """CPU-only checks of the actor library's host side: astro_amd/actor.py's numpy
 models against the reference's own EpsilonGreedy (counts in
 tests/golden/explore.npz, tools/gen_golden.py: gen_explore) and a hand-written
-schedule of game ends, include/astro_actor.h and libastro_actor.so's argument
-checks."""
+schedule of game ends, and libastro_actor.so's argument checks."""
 import ctypes
 import math
-import os
-import re
-import subprocess
-import tempfile
 from fractions import Fraction
 
 import numpy as np
@@ -18,61 +13,13 @@ import __graft_entry__
 from astro_amd import _lib, actor
 from tests import actor_util as au
 from tests import golden_io as gio
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'astro_actor.h')
-DECL = r'^\s*(?:const\s+)?\w+\s*\*?\s*(astro_\w+)\s*\('
+from tests import test_libraries as libraries
 
 
-def test_header_and_library_symbols():
-    __graft_entry__.build()
-    text = open(HEADER).read()
-    names = set(re.findall(DECL, text, re.M))
-    assert names == set(_lib._ACTOR_SYMBOLS) == {
-        'astro_actor_abi_version', 'astro_actor_last_error', 'astro_explore', 'astro_episodes'}
-    out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.ACTOR_LIB_PATH], text=True)
-    assert names == set(re.findall(r' T (astro_\w+)$', out, re.M))
-    lib = _lib.load_actor()
-    for n in names:
-        getattr(lib, n)
-    assert lib.astro_actor_abi_version() == _lib.ACTOR_ABI_VERSION == 1
-    assert '#define ASTRO_ACTOR_ABI_VERSION 1' in text
-    # the four older tables are what they were
-    assert set(_lib._REPLAY_SYMBOLS) == {
-        'astro_replay_abi_version', 'astro_replay_last_error', 'astro_replay_push',
-        'astro_replay_sample_workspace_bytes', 'astro_replay_sample', 'astro_replay_gather', 'astro_replay_update'}
-    assert set(_lib._QTRAIN_SYMBOLS) == {'astro_qtrain_abi_version', 'astro_qtrain_last_error', 'astro_qforward',
-                                         'astro_qgrad_workspace_bytes', 'astro_qgrad'}
-    assert set(_lib._QNET_SYMBOLS) == {'astro_qnet_abi_version', 'astro_qnet_last_error', 'astro_qvalues'}
-    assert set(_lib._SYMBOLS) == {
-        'astro_abi_version', 'astro_last_error', 'astro_step', 'astro_step_many', 'astro_reset', 'astro_stream_init',
-        'astro_keytable_build', 'astro_controls', 'astro_features', 'astro_host_alloc', 'astro_host_free',
-        'astro_dev_alloc', 'astro_dev_free', 'astro_game_step', 'astro_rollout'}
-    assert (_lib.ABI_VERSION, _lib.QNET_ABI_VERSION, _lib.QTRAIN_ABI_VERSION, _lib.REPLAY_ABI_VERSION) == (21, 1, 1, 1)
-    for header, table in (('astro_step.h', _lib._SYMBOLS), ('astro_qnet.h', _lib._QNET_SYMBOLS),
-                          ('astro_qtrain.h', _lib._QTRAIN_SYMBOLS), ('astro_replay.h', _lib._REPLAY_SYMBOLS)):
-        assert set(re.findall(DECL, open(os.path.join(ROOT, 'include', header)).read(), re.M)) == set(table), header
-
-
-def test_header_compiles_as_c_and_matches_the_ctypes_layout():
-    """gcc -std=c99 on include/astro_actor.h: sizeof/offsetof of both structs equal the ctypes mirrors'."""
-    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "astro_actor.h"', 'int main(void){']
-    expect = []
-    for st in (_lib.AstroExplore, _lib.AstroEpisodes):
-        lines.append('printf("%%zu\\n", sizeof(%s));' % st.__name__)
-        expect.append(ctypes.sizeof(st))
-        for f, _ in st._fields_:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (st.__name__, f))
-            expect.append(getattr(st, f).offset)
-    lines += ['printf("%d\\n", ASTRO_ACTOR_ABI_VERSION);', 'printf("%d\\n", ASTRO_EXPLORE_ONE == 9007199254740992ull);',
-              'return 0;}']
-    expect += [_lib.ACTOR_ABI_VERSION, 1]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'layout.c'), os.path.join(d, 'layout')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Werror', '-I', os.path.dirname(HEADER), src, '-o', exe])
-        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
-    assert got == expect
+def test_header_compiles_as_c_and_matches_the_ctypes_layout(tmp_path):
+    """Both structs, the ABI number and ASTRO_EXPLORE_ONE == 2^53: the actor row's layout and constants cases."""
+    libraries.test_struct_layouts_are_the_ctypes_mirrors('actor', tmp_path)
+    libraries.test_header_constants_are_the_python_ones('actor', tmp_path)
 
 
 def _explore(**kw):

@@ -1,9 +1,5 @@
 """CPU-only checks of the boundary and the host logic (no GPU needed)."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -13,56 +9,13 @@ from astro_amd import _lib, schedule, shard
 from astro_amd.config import DEFAULT_CONFIG, SOLO_CONFIG, generate_configs
 from oracle import batched
 from tests import golden_io as gio
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'astro_step.h')
+from tests import test_libraries as libraries
 
 
 @pytest.fixture(scope='module')
 def lib():
     __graft_entry__.build()
     return _lib.load()
-
-
-def _declared_functions():
-    text = open(HEADER).read()
-    return sorted(set(re.findall(r'^\s*(?:const\s+)?\w+\s*\*?\s*(astro_\w+)\s*\(', text, re.M)))
-
-
-def test_library_exports_every_header_symbol(lib):
-    names = _declared_functions()
-    assert set(names) == {'astro_abi_version', 'astro_last_error', 'astro_step', 'astro_step_many', 'astro_reset',
-                          'astro_stream_init', 'astro_keytable_build', 'astro_features', 'astro_rollout',
-                          'astro_controls', 'astro_host_alloc', 'astro_host_free', 'astro_dev_alloc',
-                          'astro_dev_free', 'astro_game_step'}
-    out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.LIB_PATH], text=True)
-    exported = set(re.findall(r' T (astro_\w+)$', out, re.M))
-    assert set(names) <= exported
-    for n in names:
-        getattr(lib, n)
-    assert lib.astro_abi_version() == _lib.ABI_VERSION
-
-
-def test_ctypes_struct_layout_matches_header():
-    """sizeof/offsetof of the C structs (gcc on include/astro_step.h) equal
-    the ctypes mirrors'."""
-    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "astro_step.h"', 'int main(void){']
-    expect = []
-    cname = {'in_': 'in'}   # (ctypes field names that are Python keywords)
-    for st in (_lib.AstroParams, _lib.AstroState, _lib.AstroPolicy, _lib.AstroGameTick):
-        lines.append('printf("%%zu\\n", sizeof(%s));' % st.__name__)
-        expect.append(ctypes.sizeof(st))
-        for f, _ in st._fields_:
-            lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (st.__name__, cname.get(f, f)))
-            expect.append(getattr(st, f).offset)
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, 'layout.c')
-        exe = os.path.join(d, 'layout')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', '-std=c99', '-I', os.path.dirname(HEADER), src, '-o', exe])
-        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
-    assert got == expect
 
 
 def test_game_step_validation_without_gpu(lib):
@@ -211,12 +164,9 @@ def test_wrap_formula_matches_numpy_remainder():
     assert ((m - np.float32(1)).view(np.int32) == (((x32 + 1) % 2) - 1).view(np.int32)).all()
 
 
-def test_kernel_choice_mirrors_header():
-    """BatchedEnv.step_kernel's AUTO rule uses the header's quad/lane crossover."""
-    from astro_amd import env as _env
-    hdr = open(os.path.join(os.path.dirname(__graft_entry__.__file__), 'include', 'astro_step.h')).read()
-    n = int(re.search(r'#define ASTRO_QUAD_MAX_ENVS (\d+)', hdr).group(1))
-    assert _env.QUAD_MAX_ENVS == n
+def test_kernel_choice_mirrors_header(tmp_path):
+    """BatchedEnv.step_kernel's AUTO rule uses the header's quad/lane crossover: a pair of the main library's constants."""
+    libraries.test_header_constants_are_the_python_ones('hip', tmp_path)
 
 
 def test_filtered_stream_oracle_matches_numpy():

@@ -1,13 +1,8 @@
 """CPU-only checks of the network-pool library's host side
-(include/astro_qpool.h, libastro_qpool.so's exports and argument codes, its
-row of the open library table), of ``league.Pool`` and its two constructors,
+(libastro_qpool.so's argument codes), of ``league.Pool`` and its two constructors,
 and of the argument rules of the pool form and of QTrainer(opponent='pool')
 that run before any device call."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
 
 import pytest
 import torch
@@ -15,67 +10,16 @@ import torch
 import __graft_entry__ as entry
 import astro_amd
 from astro_amd import BatchedEnv, _lib, league, qnet, train
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'astro_qpool.h')
-DECL = r'^\s*(?:const\s+)?\w+\s*\*?\s*(astro_\w+)\s*\('
-THREE = {'astro_qpool_abi_version', 'astro_qpool_last_error', 'astro_qvalues_pool'}
+from tests import test_libraries as libraries
 
 
-def test_header_and_library_symbols():
-    entry.build()
-    names = set(re.findall(DECL, open(HEADER).read(), re.M))
-    assert names == set(_lib._QPOOL_SYMBOLS) == THREE
-    out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.QPOOL_LIB_PATH], text=True)
-    assert set(re.findall(r' T (astro_\w+)$', out, re.M)) == THREE
-    assert _lib.load_qpool().astro_qpool_abi_version() == _lib.QPOOL_ABI_VERSION == 1
-
-
-def test_header_compiles_as_c_and_its_constants_are_the_bindings():
-    # a second declaration with the binding's argument list compiles only if it is the header's prototype
-    lines = ['#include <stdio.h>', '#include "astro_qpool.h"',
-             'int astro_qvalues_pool(const AstroParams *, const AstroState *, const AstroQNet *, int32_t,',
-             '                       const AstroQSpan *, int32_t, float *, int8_t *, const AstroPolicy *, double,',
-             '                       int32_t, void *);',
-             'int main(void){',
-             'AstroQSpan s = {1, -1, 2, 3};',
-             'printf("%d %d %d %d %d %d\\n", ASTRO_QPOOL_ABI_VERSION, ASTRO_QPOOL_MAX_NETS, ASTRO_QPOOL_MAX_SPANS, '
-             '(int)sizeof(AstroQSpan), (int)sizeof(AstroQNet), s.ship * 1000 + s.net * 100 + s.lo * 10 + s.hi);',
-             'return 0;}']
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'h.c'), os.path.join(d, 'h')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Werror', '-I', os.path.dirname(HEADER), src, '-o', exe])
-        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
-    assert got == [_lib.QPOOL_ABI_VERSION, _lib.QPOOL_MAX_NETS, _lib.QPOOL_MAX_SPANS, ctypes.sizeof(_lib.AstroQSpan),
-                   ctypes.sizeof(_lib.AstroQNet), 923]
-    assert (_lib.QPOOL_MAX_NETS, _lib.QPOOL_MAX_SPANS, ctypes.sizeof(_lib.AstroQSpan)) == (32, 64, 16)
+def test_header_compiles_as_c_and_its_constants_are_the_bindings(tmp_path):
+    """The redeclared prototype, the limits (32, 64) and AstroQSpan (16 bytes): the qpool row's prototype,
+    constants and layout cases."""
+    libraries.test_prototypes_agree_with_restype_and_argtypes('qpool', tmp_path)
+    libraries.test_header_constants_are_the_python_ones('qpool', tmp_path)
+    libraries.test_struct_layouts_are_the_ctypes_mirrors('qpool', tmp_path)
     assert [f[0] for f in _lib.AstroQSpan._fields_] == ['ship', 'net', 'lo', 'hi']
-
-
-def test_the_table_row():
-    assert list(_lib.OPEN_LIBS)[:2] == ['qduel', 'qpool']
-    L = _lib.OPEN_LIBS['qpool']
-    assert type(L) is _lib.Lib
-    assert (L.key, L.file, L.source, L.env, L.abi) == ('qpool', 'libastro_qpool.so', 'astro_qpool.hip',
-                                                      'ASTRO_QPOOL_LIB', 1)
-    assert (L.version, L.error, L.handle) == ('astro_qpool_abi_version', 'astro_qpool_last_error', '_qpool_lib')
-    assert _lib.EVERY_LIB['qpool'] is L and _lib.QPOOL_LIB_PATH is L.path and _lib._QPOOL_SYMBOLS is L.symbols
-    assert callable(_lib.load_qpool) and callable(_lib.check_qpool)
-    csrc = os.path.join(ROOT, 'astro_amd', 'csrc')
-    deps = entry.dependencies(os.path.join(csrc, L.source))
-    assert {os.path.basename(d) for d in deps} == {'astro_qpool.hip', 'astro_qpool.h', 'astro_qnet.h', 'astro_step.h',
-                                                  'astro_common.h', 'astro_qfwd.h'}
-    deps = entry.dependencies(os.path.join(csrc, 'astro_qnet.hip'))
-    assert {os.path.basename(d) for d in deps} == {'astro_qnet.hip', 'astro_qnet.h', 'astro_step.h', 'astro_common.h',
-                                                  'astro_qfwd.h'}
-    assert sorted(f for f in os.listdir(csrc) if f.endswith('.h')) == ['astro_common.h', 'astro_qfwd.h']
-    # the forward's helpers are astro_qfwd.h's: no Q-network source states them again
-    for name in ('astro_qnet.hip', 'astro_qduel.hip', L.source):
-        text = open(os.path.join(csrc, name)).read()
-        assert not re.search(r'\bfloat\s+softsign\b|\bstruct\s+WaveLds\b|\bstruct\s+Explore\b', text), name
-    entry.build()
-    assert os.path.exists(L.path)
 
 
 def test_argument_codes_without_gpu():

@@ -1,10 +1,6 @@
 """CPU-only checks of the Q-network policy's host side (astro_amd/qnet.py,
-include/astro_qnet.h, tests/golden/qnet.npz)."""
+libastro_qnet.so's argument checks, tests/golden/qnet.npz)."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -16,9 +12,7 @@ from astro_amd.config import DEFAULT_CONFIG
 from oracle import port
 from tests import golden_io as gio
 from tests import qnet_util as qu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'astro_qnet.h')
+from tests import test_libraries as libraries
 
 
 def _module(name, dtype=torch.float32):
@@ -68,38 +62,10 @@ def test_pack_unpack_round_trip(name):
         qnet.unpack(flat[:-1], S, 6)
 
 
-def test_ctypes_struct_layout_matches_header():
-    """sizeof/offsetof of AstroQNet (gcc on include/astro_qnet.h) equal the ctypes mirror's."""
-    st = _lib.AstroQNet
-    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "astro_qnet.h"', 'int main(void){',
-             'printf("%%zu\\n", sizeof(%s));' % st.__name__]
-    expect = [ctypes.sizeof(st)]
-    for f, _ in st._fields_:
-        lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (st.__name__, f))
-        expect.append(getattr(st, f).offset)
-    lines += ['printf("%d\\n", ASTRO_QNET_ABI_VERSION);', 'printf("%d\\n", ASTRO_QNET_HIDDEN);', 'return 0;}']
-    expect += [_lib.QNET_ABI_VERSION, _lib.QNET_HIDDEN]
-    with tempfile.TemporaryDirectory() as d:
-        src = os.path.join(d, 'layout.c')
-        exe = os.path.join(d, 'layout')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', '-std=c99', '-I', os.path.dirname(HEADER), src, '-o', exe])
-        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
-    assert got == expect
-
-
-def test_library_exports_every_header_symbol():
-    __graft_entry__.build()
-    text = open(HEADER).read()
-    names = sorted(set(re.findall(r'^\s*(?:const\s+)?\w+\s*\*?\s*(astro_\w+)\s*\(', text, re.M)))
-    assert set(names) == {'astro_qnet_abi_version', 'astro_qnet_last_error', 'astro_qvalues'} == set(_lib._QNET_SYMBOLS)
-    out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.QNET_LIB_PATH], text=True)
-    exported = set(re.findall(r' T (astro_\w+)$', out, re.M))
-    assert set(names) <= exported
-    lib = _lib.load_qnet()
-    for n in names:
-        getattr(lib, n)
-    assert lib.astro_qnet_abi_version() == _lib.QNET_ABI_VERSION
+def test_ctypes_struct_layout_matches_header(tmp_path):
+    """AstroQNet, the ABI number and ASTRO_QNET_HIDDEN: the qnet row's layout and constants cases."""
+    libraries.test_struct_layouts_are_the_ctypes_mirrors('qnet', tmp_path)
+    libraries.test_header_constants_are_the_python_ones('qnet', tmp_path)
 
 
 def test_bad_arguments_without_gpu():

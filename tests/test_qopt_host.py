@@ -1,11 +1,7 @@
-"""CPU-only checks of the optimiser library's host side: include/astro_qopt.h,
-libastro_qopt.so's exports and argument checks, the second library table, and
-astro_amd/optim.py's numpy mirror against torch.optim in float64."""
+"""CPU-only checks of the optimiser library's host side: libastro_qopt.so's
+argument checks and astro_amd/optim.py's numpy mirror against torch.optim in
+float64."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -13,71 +9,15 @@ import pytest
 import __graft_entry__ as entry
 from astro_amd import _lib, optim, qnet
 from tests import qopt_util as qo
+from tests import test_libraries as libraries
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'astro_qopt.h')
-DECL = r'^\s*(?:const\s+)?\w+\s*\*?\s*(astro_\w+)\s*\('
 U = 2.0 ** -24
 
 
-def test_header_and_library_symbols():
-    entry.build()
-    text = open(HEADER).read()
-    names = set(re.findall(DECL, text, re.M))
-    assert names == set(_lib._QOPT_SYMBOLS) == {'astro_qopt_abi_version', 'astro_qopt_last_error', 'astro_qopt_step'}
-    out = subprocess.check_output(['nm', '-D', '--defined-only', _lib.QOPT_LIB_PATH], text=True)
-    assert names == set(re.findall(r' T (astro_\w+)$', out, re.M))
-    lib = _lib.load_qopt()
-    assert lib.astro_qopt_abi_version() == _lib.QOPT_ABI_VERSION == 1
-    assert '#define ASTRO_QOPT_ABI_VERSION 1' in text
-
-
-def test_header_compiles_as_c_and_matches_the_ctypes_layout():
-    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "astro_qopt.h"', 'int main(void){',
-             'printf("%zu\\n", sizeof(AstroQOpt));']
-    expect = [ctypes.sizeof(_lib.AstroQOpt)]
-    for f, _ in _lib.AstroQOpt._fields_:
-        lines.append('printf("%%zu\\n", offsetof(AstroQOpt, %s));' % f)
-        expect.append(getattr(_lib.AstroQOpt, f).offset)
-    consts = ['ASTRO_QOPT_ABI_VERSION', 'ASTRO_QOPT_MAX_PARAMS', 'ASTRO_QOPT_THREADS', 'ASTRO_QOPT_SGD',
-              'ASTRO_QOPT_RMSPROP', 'ASTRO_QOPT_ADAGRAD', 'ASTRO_QOPT_ADAM']
-    lines += ['printf("%%d\\n", %s);' % c for c in consts] + ['return 0;}']
-    expect += [_lib.QOPT_ABI_VERSION, _lib.QOPT_MAX_PARAMS, _lib.QOPT_THREADS] + [
-        _lib.QOPT_KINDS[k] for k in ('sgd', 'rmsprop', 'adagrad', 'adam')]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'layout.c'), os.path.join(d, 'layout')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Werror', '-I', os.path.dirname(HEADER), src, '-o', exe])
-        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
-    assert got == expect
-    assert ctypes.sizeof(_lib.AstroQOpt) == 64 and optim.THREADS == 1024
-
-
-def test_the_second_table():
-    assert tuple(_lib.LATER_LIBS) == ('qopt',)
-    L = _lib.LATER_LIBS['qopt']
-    assert (L.key, L.file, L.source, L.env, L.abi) == ('qopt', 'libastro_qopt.so', 'astro_qopt.hip', 'ASTRO_QOPT_LIB', 1)
-    assert (L.version, L.error, L.handle) == ('astro_qopt_abi_version', 'astro_qopt_last_error', '_qopt_lib')
-    assert list(_lib.ALL_LIBS.items()) == list(_lib.LIBS.items()) + list(_lib.LATER_LIBS.items())
-    assert type(L) is _lib.Lib and not set(_lib.LIBS) & set(_lib.LATER_LIBS)
-    assert _lib.QOPT_LIB_PATH is L.path and _lib.QOPT_ABI_VERSION is L.abi and _lib._QOPT_SYMBOLS is L.symbols
-    assert L.path == os.environ.get(L.env) or L.path == os.path.join(ROOT, 'astro_amd', L.file)
-    assert set(L.symbols) >= {L.version, L.error}
-    assert callable(_lib.load_qopt) and callable(_lib.check_qopt) and hasattr(_lib, '_qopt_lib')
-    # the source's dependencies are the headers it reaches, by a walk of its own
-    src = os.path.join(ROOT, 'astro_amd', 'csrc', L.source)
-    want = {src}
-    for line in open(src):
-        m = re.match(r'\s*#\s*include\s*"([^"]+)"', line)
-        if m:
-            want.add([p for p in (os.path.join(ROOT, 'include', m.group(1)),
-                                  os.path.join(ROOT, 'astro_amd', 'csrc', m.group(1))) if os.path.exists(p)][0])
-    deps = entry.dependencies(src)
-    assert len(deps) == len(set(deps)) and set(deps) == want
-    assert {os.path.basename(d) for d in deps} == {'astro_qopt.hip', 'astro_qopt.h', 'astro_common.h'}
-    for h in ('astro_qopt.h', 'astro_common.h'):     # neither includes a project header of its own
-        path = [d for d in deps if os.path.basename(d) == h][0]
-        assert not re.search(r'^\s*#\s*include\s*"', open(path).read(), re.M)
+def test_header_compiles_as_c_and_matches_the_ctypes_layout(tmp_path):
+    """AstroQOpt (64 bytes), the ABI number, the kinds and limits: the qopt row's layout and constants cases."""
+    libraries.test_struct_layouts_are_the_ctypes_mirrors('qopt', tmp_path)
+    libraries.test_header_constants_are_the_python_ones('qopt', tmp_path)
 
 
 def _opt(**kw):

@@ -1,6 +1,5 @@
-"""CPU-only checks of the trace library's host side (include/astro_trace.h,
-libastro_trace.so's exports and argument codes, its row of the library table)
-and of astro_amd/record.py's host half: ``decode`` against play-throughs of
+"""CPU-only checks of the trace library's host side (libastro_trace.so's
+argument codes) and of astro_amd/record.py's host half: ``decode`` against play-throughs of
 the numpy oracle packed into the ring's layout by hand, the log round trip
 with Q values, and the Recorder's argument checks that run before any device
 call."""
@@ -8,9 +7,6 @@ import ctypes
 import gzip
 import json
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -22,62 +18,22 @@ from astro_amd import (BatchedEnv, DEFAULT_CONFIG, SOLO_CONFIG, SOLO_EASY_CONFIG
                        schedule as _schedule)
 from oracle import port
 from tests import golden_io as gio
+from tests import test_libraries as libraries
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'astro_trace.h')
-DECL = r'^\s*(?:const\s+)?\w+\s*\*?\s*(astro_\w+)\s*\('
-FOUR = {'astro_trace_abi_version', 'astro_trace_last_error', 'astro_trace_state', 'astro_trace_result'}
 FIELDS = ('ids', 'ships', 'ships_b', 'planets', 'bullets', 'hdr', 'control', 'q', 'reward', 'done', 'm', 'ticks',
           'nout', 'reserved')
 
 
 # ---------------------------------------------------------------------------
-# the library: table row, header, argument codes
+# the library: header, argument codes
 
-def test_the_table_row():
-    assert list(_lib.OPEN_LIBS)[:2] == ['qduel', 'qpool'] and list(_lib.OPEN_LIBS)[2] == 'trace'
-    L = _lib.OPEN_LIBS['trace']
-    assert type(L) is _lib.Lib and _lib.EVERY_LIB['trace'] is L
-    assert (L.key, L.file, L.source, L.env, L.abi) == ('trace', 'libastro_trace.so', 'astro_trace.hip',
-                                                      'ASTRO_TRACE_LIB', 1)
-    assert (L.version, L.error, L.handle) == ('astro_trace_abi_version', 'astro_trace_last_error', '_trace_lib')
-    assert hasattr(_lib, '_trace_lib') and set(L.symbols) == FOUR and L.symbols is _lib._TRACE_SYMBOLS
-    assert _lib.TRACE_LIB_PATH is L.path and _lib.TRACE_ABI_VERSION == 1
-    assert callable(_lib.load_trace) and callable(_lib.check_trace)
-    deps = entry.dependencies(os.path.join(ROOT, 'astro_amd', 'csrc', L.source))
-    assert sorted(os.path.basename(d) for d in deps) == ['astro_common.h', 'astro_step.h', 'astro_trace.h',
-                                                         'astro_trace.hip']
-    assert os.path.dirname(HEADER) == entry.INCLUDE
-    entry.build()
-    assert os.path.exists(L.path)
-    names = set(re.findall(DECL, open(HEADER).read(), re.M))
-    assert names == FOUR
-    out = subprocess.check_output(['nm', '-D', '--defined-only', L.path], text=True)
-    assert set(re.findall(r' T (astro_\w+)$', out, re.M)) == FOUR
-    assert _lib.load_trace().astro_trace_abi_version() == 1
-
-
-def test_header_compiles_as_c99_and_the_struct_is_the_mirror():
+def test_header_compiles_as_c99_and_the_struct_is_the_mirror(tmp_path):
+    """AstroTrace, the two redeclared prototypes and ASTRO_TRACE_MAX_OUT: the trace row's layout, prototype
+    and constants cases."""
     assert tuple(n for n, _ in _lib.AstroTrace._fields_) == FIELDS
-    offs = ', '.join('(int)offsetof(AstroTrace, %s)' % f for f in FIELDS)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "astro_trace.h"',
-             # a second declaration with the binding's argument list compiles only if it is the header's prototype
-             'int astro_trace_state(const AstroParams *, const AstroState *, const AstroTrace *, int32_t,',
-             '                      const int8_t *, const float *, void *);',
-             'int astro_trace_result(const AstroTrace *, int32_t, const float *, const uint8_t *, int32_t, int32_t,',
-             '                       void *);',
-             'int main(void){',
-             'int o[] = {%s};' % offs,
-             'printf("%d %d %d", ASTRO_TRACE_ABI_VERSION, ASTRO_TRACE_MAX_OUT, (int)sizeof(AstroTrace));',
-             'for (unsigned k = 0; k < sizeof o / sizeof *o; ++k) printf(" %d", o[k]);',
-             'return 0;}']
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, 'h.c'), os.path.join(d, 'h')
-        open(src, 'w').write('\n'.join(lines))
-        subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Werror', '-I', os.path.dirname(HEADER), src, '-o', exe])
-        got = [int(x) for x in subprocess.check_output([exe], text=True).split()]
-    assert got[:3] == [_lib.TRACE_ABI_VERSION, _lib.TRACE_MAX_OUT, ctypes.sizeof(_lib.AstroTrace)]
-    assert got[3:] == [getattr(_lib.AstroTrace, f).offset for f in FIELDS]
+    libraries.test_struct_layouts_are_the_ctypes_mirrors('trace', tmp_path)
+    libraries.test_prototypes_agree_with_restype_and_argtypes('trace', tmp_path)
+    libraries.test_header_constants_are_the_python_ones('trace', tmp_path)
 
 
 def _params(**kw):
