@@ -9,6 +9,8 @@ bookkeeping, ``QTrainer`` (train.py) the training loop made of them, ``SGD``,
 ``RMSprop``, ``Adagrad`` and ``Adam`` (optim.py) its update rules, ``league``
 (league.py) the comparison of networks: ``p_better``, ``find_better``,
 ``compare``, and ``Pool`` / ``tournament`` for many networks on one env,
+``Script`` / ``Seats`` for scripted bots with their own arguments per ship and
+env block next to them, and ``mutate`` / ``tune_script``, ScriptBot's tuning walk,
 ``Recorder`` (record.py) whole games of chosen envs recorded on the device, as
 the reference's ``Game`` / ``Tick`` logs with the networks' Q values.
 """
@@ -20,6 +22,7 @@ from .actor import EpsilonGreedy, Episodes  # noqa: F401
 from .optim import SGD, Adagrad, Adam, RMSprop  # noqa: F401
 from .train import QTrainer  # noqa: F401
 from . import league  # noqa: F401
-from .league import Pool, compare, find_better, p_better, tournament  # noqa: F401
+from .league import (Pool, Script, Seats, compare, find_better, mutate, p_better, tournament,  # noqa: F401
+                     tune_script)
 from . import record  # noqa: F401
 from .record import Recorder  # noqa: F401

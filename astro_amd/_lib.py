@@ -10,6 +10,7 @@
     qduel   libastro_qduel.so    astro_qduel.h
     qpool   libastro_qpool.so    astro_qpool.h
     trace   libastro_trace.so    astro_trace.h
+    seats   libastro_seats.so    astro_seats.h
 
 The libraries are built in-tree by ``__graft_entry__.build()`` (hipcc
 --offload-arch=gfx950).  There is no fallback: if a library is missing or its
@@ -391,6 +392,32 @@ _TRACE_SYMBOLS = {
 }
 
 
+class AstroSeat(ctypes.Structure):
+    """include/astro_seats.h AstroSeat: ship ``ship`` of the envs [lo, hi) is played by bot ``bot`` (a value of
+    BOTS, or -1: skipped), a script bot with these two arguments."""
+    _fields_ = [
+        ('ship', ctypes.c_int32),
+        ('bot', ctypes.c_int32),
+        ('lo', ctypes.c_int32),
+        ('hi', ctypes.c_int32),
+        ('script_r2', ctypes.c_double),
+        ('script_threshold', ctypes.c_double),
+    ]
+
+
+SEATS_MAX = 64          # include/astro_seats.h ASTRO_SEATS_MAX
+
+# libastro_seats.so: scripted bots with their own arguments per ship and env block, a library of its own
+# (include/astro_seats.h)
+_SEATS_SYMBOLS = {
+    'astro_seats_abi_version': (ctypes.c_int, []),
+    'astro_seats_last_error': (ctypes.c_char_p, []),
+    'astro_controls_seats': (ctypes.c_int, [ctypes.POINTER(AstroParams), ctypes.POINTER(AstroState),
+                                            ctypes.POINTER(AstroPolicy), ctypes.POINTER(AstroSeat), ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+}
+
+
 class AstroError(RuntimeError):
     pass
 
@@ -417,6 +444,7 @@ LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qduel', 'libastro_qduel.so', 'astro_qduel.hip', 'ASTRO_QDUEL_LIB', 1, 'astro_qduel_', _QDUEL_SYMBOLS),
     _row('qpool', 'libastro_qpool.so', 'astro_qpool.hip', 'ASTRO_QPOOL_LIB', 1, 'astro_qpool_', _QPOOL_SYMBOLS),
     _row('trace', 'libastro_trace.so', 'astro_trace.hip', 'ASTRO_TRACE_LIB', 1, 'astro_trace_', _TRACE_SYMBOLS),
+    _row('seats', 'libastro_seats.so', 'astro_seats.hip', 'ASTRO_SEATS_LIB', 1, 'astro_seats_', _SEATS_SYMBOLS),
 ))
 LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
 QNET_LIB_PATH, QNET_ABI_VERSION = LIBS['qnet'].path, LIBS['qnet'].abi
@@ -427,10 +455,11 @@ QOPT_LIB_PATH, QOPT_ABI_VERSION = LIBS['qopt'].path, LIBS['qopt'].abi
 QDUEL_LIB_PATH, QDUEL_ABI_VERSION = LIBS['qduel'].path, LIBS['qduel'].abi
 QPOOL_LIB_PATH, QPOOL_ABI_VERSION = LIBS['qpool'].path, LIBS['qpool'].abi
 TRACE_LIB_PATH, TRACE_ABI_VERSION = LIBS['trace'].path, LIBS['trace'].abi
+SEATS_LIB_PATH, SEATS_ABI_VERSION = LIBS['seats'].path, LIBS['seats'].abi
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
 _lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = None
-_qopt_lib = _qduel_lib = _qpool_lib = _trace_lib = None
+_qopt_lib = _qduel_lib = _qpool_lib = _trace_lib = _seats_lib = None
 
 
 def _load(key, path):
@@ -490,6 +519,7 @@ load_qopt, check_qopt = _public('qopt')
 load_qduel, check_qduel = _public('qduel')
 load_qpool, check_qpool = _public('qpool')
 load_trace, check_trace = _public('trace')
+load_seats, check_seats = _public('seats')
 
 
 def stream_ptr(device):

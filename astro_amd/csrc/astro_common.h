@@ -66,6 +66,99 @@ __device__ __forceinline__ C norm_angle_over_pi(C b) {
 }
 
 // ---------------------------------------------------------------------------
+// script.ScriptBot (script.py:13-91) on the bot's ego view (core.roll_ships:
+// its own ship first), in the precision numpy evaluates it for the state's
+// dtypes (NEP 50: Python-float constants take the array's dtype):
+//   X -- ship positions, velocities and bearings, and ship - planet
+//        positions: float32 at a game's first tick (create()'s arrays),
+//        float64 after;
+//   V -- ship - planet velocities: float32 only at the first tick of a
+//        one-planet game (its planet's dx is float32 for ever), else float64.
+// Scalar ** 2 in the reference is pow(x, 2); x * x here (they differ only
+// where pow is not correctly rounded).
+// D holds the bot's six constants as AstroPolicy names them (script_r2,
+// script_threshold, ship_thrust, ship_rspeed, bullet_speed, ship_radius): the
+// step library's TickDriver, astro_seats.hip's per-ship seat record.
+
+__device__ __forceinline__ float np_atan2(float y, float x) { return atan2f(y, x); }
+__device__ __forceinline__ double np_atan2(double y, double x) { return atan2(y, x); }
+
+// ScriptBot._fly_to (script.py:26-35); t is a value of the angle's dtype
+template <typename C>
+__device__ __forceinline__ int fly_to(C target, C bearing, C t, bool fwd) {
+    const C angle = np_norm_angle<C>(target - bearing);
+    if (angle < -t) return 0;   // rotate left
+    if (t < angle) return 4;    // rotate right
+    return fwd ? 3 : 2;
+}
+
+// ScriptBot._danger (script.py:37-62) for one planet: true with the bearing
+// to steer for when the course meets the inflated planet soon.  (As in the
+// reference, `b` is rebound to the quadratic's linear coefficient before the
+// rotation estimate uses it.)
+template <typename X, typename V, typename D>
+__device__ __forceinline__ bool script_danger(const D &d, X rx, X ry, V rvx, V rvy, X &steer) {
+    using L = typename std::conditional<(sizeof(X) >= sizeof(V)), X, V>::type;
+    const V speed = sqrt(rvx * rvx + rvy * rvy);            // util.mag(dx)
+    const V den = speed + V(1e-12);                          // util.norm(dx)
+    const V nx = rvx / den, ny = rvy / den;
+    const L lin = L(2) * (L(nx) * L(rx) + L(ny) * L(ry));   // 2 * util.dot(norm(dx), x)
+    const X mag = sqrt(rx * rx + ry * ry);
+    const X c = mag * mag - X(d.script_r2);
+    const L det = lin * lin - L(X(4) * c);
+    if (!(L(0) < det)) return false;
+    const L sq = sqrt(det);
+    if (!(L(0) <= -lin + sq)) return false;
+    const L distance = -lin - sq;
+    const X bx = np_atan2(rx, ry);                           // util.bearing(x)
+    const L rotation = fabs(np_norm_angle<L>(L(bx) - lin));
+    const L reach = (L(speed / V(d.ship_thrust)) + L(d.ship_rspeed) / rotation) * L(speed);
+    if (!(distance < reach)) return false;
+    steer = bx;
+    return true;
+}
+
+// ScriptBot.__call__ (script.py:64-91): (m*) the bot's own ship, (e*) the
+// other ship (two-ship games), planets j < np
+template <typename X, typename V, int S, int PMAX, typename D>
+__device__ __forceinline__ int script_decide(const D &d, bool solo, int np, const double (&px)[PMAX],
+                                          const double (&py)[PMAX], const double (&pdx)[PMAX],
+                                          const double (&pdy)[PMAX], double mx, double my, double mdx,
+                                          double mdy, double mb, double ex, double ey, double edx, double edy) {
+    for (int j = 0; j < PMAX; ++j) {   // don't crash into planets (in index order)
+        X steer;
+        if (j < np && script_danger<X, V>(d, X(mx) - X(px[j]), X(my) - X(py[j]), V(mdx) - V(pdx[j]),
+                                          V(mdy) - V(pdy[j]), steer))
+            return fly_to<X>(steer, X(mb), X(d.script_threshold), true);
+    }
+    if (S == 1 || solo) return 2;      // no enemy to aim for
+    // aim for the enemy: where it will be when a bullet gets there
+    const X dx = X(ex) - X(mx), dy = X(ey) - X(my);
+    const X distance = sqrt(dx * dx + dy * dy);
+    const X flight = distance / X(d.bullet_speed);
+    const X fx = X(ex) + flight * (X(edx) - X(mdx));
+    const X fy = X(ey) + flight * (X(edy) - X(mdy));
+    return fly_to<X>(np_atan2(fx - X(mx), fy - X(my)), X(mb), X(d.ship_radius) / distance, false);
+}
+
+// dtype dispatch: X float32 at tick 0, V float32 at tick 0 of a one-planet game
+template <int S, int PMAX, typename D>
+__device__ __forceinline__ int script_control(const D &d, bool solo, bool t0, int np,
+                                              const double (&px)[PMAX], const double (&py)[PMAX],
+                                              const double (&pdx)[PMAX], const double (&pdy)[PMAX], double mx,
+                                              double my, double mdx, double mdy, double mb, double ex, double ey,
+                                              double edx, double edy) {
+    if (!t0)
+        return script_decide<double, double, S, PMAX>(d, solo, np, px, py, pdx, pdy, mx, my, mdx, mdy, mb, ex, ey,
+                                                      edx, edy);
+    if (np == 1)
+        return script_decide<float, float, S, PMAX>(d, solo, np, px, py, pdx, pdy, mx, my, mdx, mdy, mb, ex, ey,
+                                                    edx, edy);
+    return script_decide<float, double, S, PMAX>(d, solo, np, px, py, pdx, pdy, mx, my, mdx, mdy, mb, ex, ey,
+                                                 edx, edy);
+}
+
+// ---------------------------------------------------------------------------
 // the random word behind every random decision: splitmix64 of
 // id * 0x9E37... + (draw + 1) * 0xD1B5... + seed
 

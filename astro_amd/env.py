@@ -36,7 +36,7 @@ from . import _lib
 from . import shard as _shard
 from .config import nships as _nships, reference_state as _reference_state
 from . import schedule as _schedule
-from .league import Pool
+from .league import Pool, Script, Seats
 
 TICK_MASK = (1 << 22) - 1
 MT_N = 624   # MT19937 state words: each env's seed stream keeps its own (stream_ring)
@@ -541,6 +541,11 @@ class BatchedEnv:
             _lib.stream_ptr(self.device)), 'astro_qvalues_pool')
 
     def _qvalues(self, net, q, control, explore, epsilon):
+        if type(net) is Seats:   # its networks' part; the scripted seats are seat_controls'
+            self._check_seats(net)
+            if net.pool is not None:
+                self._qvalues_pool(net.pool, q, control, explore, epsilon)
+            return
         if type(net) is Pool:
             return self._qvalues_pool(net, q, control, explore, epsilon)
         nets = self._per_ship(net)
@@ -556,6 +561,8 @@ class BatchedEnv:
             _lib.stream_ptr(self.device)), 'astro_qvalues')
 
     def _q_buffer(self, net, out):
+        if type(net) is Seats and net.nout is None:
+            raise ValueError('these Seats hold no network: there are no Q values')
         nets = self._per_ship(net)
         nout = net.nout if nets is None else [n for n in nets if n is not None][0].nout   # (a Pool has nout too)
         shape = (self.n_env, self.S, nout)
@@ -564,6 +571,36 @@ class BatchedEnv:
         if (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
                 or not out.is_contiguous()):
             raise ValueError('out must be a contiguous float32 %s tensor on %s' % (list(shape), self.device))
+        return out
+
+    def _check_seats(self, seats):
+        if type(seats) is not Seats:
+            raise ValueError('seats must be a league.Seats')
+        if (seats.n_env, seats.S, seats.device) != (self.n_env, self.S, self.hdr.device):
+            raise ValueError('the seats were made for %d envs of %d ships on %s, this env has %d of %d on %s'
+                             % (seats.n_env, seats.S, seats.device, self.n_env, self.S, self.hdr.device))
+
+    def seat_controls(self, seats, seed=0, tick0=0, out=None):
+        """The scripted seats of a ``league.Seats`` of this env's shape, in one
+        launch (astro_controls_seats, include/astro_seats.h): every scripted
+        seat's ship of its envs gets the control ``controls`` gives there for
+        that seat's bot -- a 'script' seat with the seat's own ScriptBot
+        arguments, a 'random' seat the draw of ``controls('random', seed,
+        tick0)`` -- bit for bit.  Written into ``out``, an int8 [N, S] tensor
+        whose other entries keep their bytes, or into a fresh one (whose other
+        entries are unspecified).  The seats' networks are not evaluated:
+        ``qcontrols`` does both."""
+        self._check_seats(seats)
+        if out is None:
+            out = torch.empty((self.n_env, self.S), dtype=torch.int8, device=self.device)
+        elif (tuple(out.shape) != (self.n_env, self.S) or out.dtype != torch.int8 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError('out must be a contiguous int8 [%d, %d] tensor on %s' % (self.n_env, self.S, self.device))
+        if seats._seats is not None:
+            base = self.policy('nothing', seed, tick0)
+            _lib.check_seats(_lib.load_seats().astro_controls_seats(
+                ctypes.byref(self.params), ctypes.byref(self.state), ctypes.byref(base), seats._seats,
+                len(seats._seats), out.data_ptr(), _lib.stream_ptr(self.device)), 'astro_controls_seats')
         return out
 
     def qvalues(self, net, out=None):
@@ -587,7 +624,8 @@ class BatchedEnv:
         span's network, again bit for bit what ``qvalues`` of that network
         gives there, in one kernel (astro_qvalues_pool,
         include/astro_qpool.h).  What no span with a network covers is treated
-        like a None ship."""
+        like a None ship.  A ``league.Seats`` is its ``pool``: scripted ships
+        have no Q rows (ValueError if it holds no network)."""
         q = self._q_buffer(net, out)
         self._qvalues(net, q, None, None, 0.0)
         return q
@@ -608,7 +646,14 @@ class BatchedEnv:
         ``explore`` apply to every ship.  A None ship's rows of ``q_out`` keep
         what they held, and its column of the returned controls is
         unspecified (the tensor comes from ``torch.empty``; ``explore`` may
-        still write a held control there): fill it before stepping."""
+        still write a held control there): fill it before stepping.
+
+        A ``league.Seats`` of this env's shape: its pool's launch (if it holds
+        a network), then ``explore.apply``, then ``seat_controls(net, seed,
+        tick0, out=control)`` -- a scripted seat's control is final, exploration
+        never alters it (its state still advances, as with ``opponent='script'``
+        in ``rollout_q``); scripted ships' rows of ``q_out`` keep what they
+        held, and ``q_out`` needs a network among the seats."""
         if explore is not None and epsilon != 0.0:
             raise ValueError('pass either epsilon or explore, not both')
         net = self._per_ship(net) or net
@@ -623,6 +668,8 @@ class BatchedEnv:
             if explore.env is not self:
                 raise ValueError('explore belongs to another env')
             explore.apply(control, tick0)
+        if type(net) is Seats:
+            self.seat_controls(net, seed, tick0, out=control)
         return control
 
     def _check_opponent(self, opponent):
@@ -643,7 +690,7 @@ class BatchedEnv:
         if opponent is None:
             nets = self._per_ship(net)
             return (net if nets is None else nets), None
-        if isinstance(net, (list, tuple, Pool)):
+        if isinstance(net, (list, tuple, Pool, Seats)):
             raise ValueError('opponent goes with one QNetwork, not with the per-ship form or a Pool')
         if isinstance(opponent, str):
             return self._per_ship((net, None)), opponent
@@ -668,11 +715,13 @@ class BatchedEnv:
             raise ValueError('every ship needs a network (or name a scripted opponent)')
         if type(net) is Pool and not net.covered:
             raise ValueError('every ship of every env needs a network: the pool leaves some uncovered')
+        if type(net) is Seats and not net.covered:
+            raise ValueError('every ship of every env needs a player: the seats leave some uncovered')
         reward = torch.empty((ticks, self.n_env, self.S), dtype=torch.float32, device=self.device)
         done = torch.empty((ticks, self.n_env), dtype=torch.uint8, device=self.device)
         control = torch.empty((ticks, self.n_env, self.S), dtype=torch.int8, device=self.device)
         for t in range(ticks):
-            c = self.qcontrols(net, epsilon, seed, tick0 + t, explore=explore)
+            c = self.qcontrols(net, epsilon, seed, tick0 + t, explore=explore)   # (a Seats' scripted part included)
             if bot is not None:
                 c[:, 1] = self.controls(bot, seed, tick0 + t)[:, 1]
             control[t] = c
@@ -710,6 +759,8 @@ class BatchedEnv:
             raise ValueError('every ship needs a network (or name a scripted opponent)')
         if type(net) is Pool and not net.covered:
             raise ValueError('every ship of every env needs a network: the pool leaves some uncovered')
+        if type(net) is Seats and not net.covered:
+            raise ValueError('every ship of every env needs a player: the seats leave some uncovered')
         q_out = played = None
         if record is not None:
             if getattr(record, 'env', None) is not self:
@@ -718,8 +769,16 @@ class BatchedEnv:
                 raise ValueError('play_q drains the recorder every 64 ticks: it needs ticks >= 64, got %d'
                                  % record.ticks)
             if record.wants_q:   # a scripted opponent's ship has no network: its rows stay zero and are not reported
-                q_out = torch.zeros(self._q_buffer(net, None).shape, dtype=torch.float32, device=self.device)
-                played = [True] * self.S if bot is None else [True, False]
+                if type(net) is Seats:   # per recorded env and ship: a network's seat or a scripted one
+                    if net.nout is not None:
+                        q_out = torch.zeros(self._q_buffer(net, None).shape, dtype=torch.float32, device=self.device)
+                        played = np.zeros((self.n_env, self.S), dtype=bool)
+                        for ship, lo, hi, k in net.spans:
+                            played[lo:hi, ship] = k is not None and not isinstance(net.players[k], (str, Script))
+                        played = played[np.asarray(record.ids)]
+                else:
+                    q_out = torch.zeros(self._q_buffer(net, None).shape, dtype=torch.float32, device=self.device)
+                    played = [True] * self.S if bot is None else [True, False]
         G = int(games)
         ep = actor.Episodes(self, G)
         limit = max_ticks if max_ticks is not None else G * (self.schedule.timeout_tick + 1) + 64
@@ -728,7 +787,7 @@ class BatchedEnv:
             if t >= limit:
                 raise RuntimeError('play_q: games did not finish within %d ticks' % limit)
             for _ in range(64):
-                c = self.qcontrols(net, tick0=t, explore=explore, q_out=q_out)
+                c = self.qcontrols(net, seed=seed, tick0=t, explore=explore, q_out=q_out)
                 if bot is not None:
                     c[:, 1] = self.controls(bot, seed, t)[:, 1]
                 if record is not None:

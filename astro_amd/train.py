@@ -49,7 +49,13 @@ class QTrainer:
     optimisation step the oldest slot is refreshed with ``copy_from(net)``,
     round robin from slot 0 -- self-play against copies of oneself of K
     different ages.  pool_size=1 is 'snapshot' bit for bit.  pool_size goes with
-    'pool' only."""
+    'pool' only.  opponent=<league.Script>: ship 1 plays a ScriptBot with those
+    arguments.  opponent=<list or tuple> of ``QNetwork``s, ``Script``s and bot
+    names: a fixed ladder, ``self.ladder`` -- ship 1 of the j-th of K blocks of
+    envs plays ``opponent[j]`` (``league.Seats.versus``: the networks' launch,
+    the exploration, then one astro_controls_seats launch, astro_seats.h;
+    exploration never alters a scripted seat's control).  ``['script']`` acts as
+    'script' does, bit for bit."""
 
     def __init__(self, env, net, buf, explore, n_samples=1024, n_ministeps=1, lr=1e-2, seed=0,
                  optimizer=None, target_sync=None, double=False, opponent=None, opponent_sync=None, pool_size=None):
@@ -72,7 +78,18 @@ class QTrainer:
             else:
                 raise ValueError('target_sync must be an int >= 1 (steps between hard copies) or a float in (0, 1)')
             self.target = net.clone()
-        self.rival, self.rival_every, self.rivals = None, None, None
+        self.rival, self.rival_every, self.rivals, self.ladder = None, None, None, None
+        from .league import Script, Seats
+        if isinstance(opponent, (Script, list, tuple)):   # one scripted rival with its own arguments, or a fixed ladder
+            if pool_size is not None:
+                raise ValueError("pool_size goes with opponent='pool' only")
+            if opponent_sync is not None:
+                raise ValueError("opponent_sync goes with opponent='snapshot' or 'pool' only")
+            if env.S != 2:
+                raise ValueError('opponent needs a two-ship env')
+            self.ladder = (opponent,) if isinstance(opponent, Script) else tuple(opponent)
+            self._acting, self._bot = Seats.versus(env, net, self.ladder), None
+            return
         pool = isinstance(opponent, str) and opponent == 'pool'
         if pool_size is not None and not pool:
             raise ValueError("pool_size goes with opponent='pool' only")
@@ -123,7 +140,7 @@ class QTrainer:
         env, net, buf = self.env, self.net, self.buf
         t = buf.t
         env.features(out=buf.head())
-        control = env.qcontrols(self._acting, tick0=t, explore=self.explore)
+        control = env.qcontrols(self._acting, seed=self.seed, tick0=t, explore=self.explore)   # (seed: a Seats' 'random')
         if self._bot is not None:
             control[:, 1] = env.controls(self._bot, self.seed, t)[:, 1]
         _, reward, done = env.step(control)

@@ -670,6 +670,42 @@ def gen_script_controls():
 
 
 # ---------------------------------------------------------------------------
+# 8b. ScriptBot with non-default arguments: its decision on every input state
+#     of steps.npz, both ego views, for six (avoid_distance, avoid_threshold)
+#     sets, and an eight-step ScriptBot.mutate chain (script.py:93-108)
+
+SCRIPT_ARG_SETS = [(0.0, 0.45), (0.3, 0.45), (0.1, 0.05), (0.1, 1.5), (-0.1, 0.9), (0.2371, 0.3119)]
+
+
+def gen_script_args():
+    z = load_fixture('steps.npz')
+    names = list(z['cfg_names'])
+    n = z['tick'].shape[0]
+    out = np.full((len(SCRIPT_ARG_SETS), n, S_PAD), -1, dtype=np.int8)
+    for a, (distance, threshold) in enumerate(SCRIPT_ARG_SETS):
+        args = dict(avoid_distance=distance, avoid_threshold=threshold)
+        bots = {}
+        for i in range(n):
+            name = names[z['cfg'][i]]
+            if name not in bots:
+                bots[name] = script.ScriptBot.create(CONFIGS[name], args)
+            state = _steps_state(z, i)
+            for k in range(int(z['nships'][i])):
+                out[a, i, k] = bots[name](core.roll_ships(state, k))
+    random = np.random.RandomState(42)
+    args = dict(script.ScriptBot.DEFAULT_ARGS)
+    chain = [[args['avoid_distance'], args['avoid_threshold']]]
+    for _ in range(8):
+        args = script.ScriptBot.mutate(args, scale=0.05, random=random)
+        chain.append([args['avoid_distance'], args['avoid_threshold']])
+    save_npz_fixed(os.path.join(OUT, 'script_args.npz'),
+                   dict(args=np.array(SCRIPT_ARG_SETS, dtype=np.float64), control=out,
+                        mutate_chain=np.array(chain, dtype=np.float64), mutate_seed=np.array(42),
+                        mutate_scale=np.array(0.05)))
+    print('wrote script_args.npz', out.shape)
+
+
+# ---------------------------------------------------------------------------
 # 9. BASELINE.json config 1: DEFAULT_CONFIG (seed 42), 1000 ticks of
 #    RandomState(0).randint(0, 6, (1000, 2)) controls, re-created on done
 
@@ -1314,6 +1350,9 @@ def generate():
     if sys.argv[1:] == ['script']:
         gen_script_controls()
         return
+    if sys.argv[1:] == ['script_args']:
+        gen_script_args()
+        return
     if sys.argv[1:] == ['features']:
         gen_features()
         return
@@ -1337,6 +1376,7 @@ def generate():
     gen_qnet()
     gen_log()
     gen_script_controls()
+    gen_script_args()
     gen_config1()
     gen_long_games()
     gen_replay()

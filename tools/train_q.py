@@ -70,6 +70,11 @@ def main():
     ap.add_argument('--opponent-sync', type=int, default=None,
                     help='with --opponent snapshot / pool: steps between refreshes')
     ap.add_argument('--pool-size', type=int, default=None, help='with --opponent pool: the number of frozen copies')
+    ap.add_argument('--ladder', default=None,
+                    help="a fixed ladder of scripted rivals instead of --opponent: comma-separated rungs, each 'nothing', "
+                         "'random', 'script' or DISTANCE:THRESHOLD (a ScriptBot with those avoid_distance / "
+                         "avoid_threshold), e.g. nothing,0.0:1.5,0.05:0.9,script; ship 1 of block j of the envs plays "
+                         "rung j (league.Seats.versus), and every validation also plays each rung")
     ap.add_argument('--tournament', type=int, default=0,
                     help='M in 2..6: after the run, league.tournament over M of the validations\' networks (evenly '
                          'spaced, first and last included) on a fresh evaluation env; recorded as "tournament"')
@@ -96,8 +101,13 @@ def main():
         opt = {'sgd': lambda: optim.SGD(**common), 'momentum': lambda: optim.SGD(momentum=0.9, **common),
                'rmsprop': lambda: optim.RMSprop(**common), 'adagrad': lambda: optim.Adagrad(**common),
                'adam': lambda: optim.Adam(**common)}[args.optimizer]()
+    ladder = None
+    if args.ladder:
+        assert args.opponent is None, '--ladder goes without --opponent'
+        ladder = [r if ':' not in r else league.Script(*map(float, r.split(':'))) for r in args.ladder.split(',')]
     tr = train.QTrainer(env, net, buf, eg, n_samples=args.n_samples, lr=args.lr, seed=args.seed, optimizer=opt,
-                        target_sync=sync, double=args.double, opponent=args.opponent, opponent_sync=args.opponent_sync,
+                        target_sync=sync, double=args.double, opponent=ladder or args.opponent,
+                        opponent_sync=args.opponent_sync,
                         pool_size=args.pool_size)
     checkpoints = []                               # (tick, the network then), one per validation
     eval_cfg = DEFAULT_CONFIG._replace(max_time=args.max_time)
@@ -125,6 +135,15 @@ def main():
             point[opponent] = tr.validate(ev, games=args.games, opponent=opponent, record=rec)
             if rec is not None:
                 point['logs'] = len(rec.save(os.path.join(args.log_dir, str(tick))))
+        if ladder:   # every rung, in blocks of one evaluation batch
+            ev = BatchedEnv(eval_cfg, args.eval_envs, device=dev, b_cap=32, env_offset=1 << 20)
+            ev.reset()
+            w = ev.play_q(league.Seats.versus(ev, net, ladder), games=args.games)[0]
+            K, N = len(ladder), args.eval_envs
+            point['ladder'] = [dict(rung=args.ladder.split(',')[j],
+                                    won=float((w[j * N // K:(j + 1) * N // K] == 0).float().mean()),
+                                    lost=float((w[j * N // K:(j + 1) * N // K] == 1).float().mean()))
+                               for j in range(K)]
         if tick:
             point['vs_previous'], point['vs_first'] = against(previous), against(first)
             previous.copy_from(net)
