@@ -12,7 +12,9 @@ bookkeeping, ``QTrainer`` (train.py) the training loop made of them, ``SGD``,
 ``Script`` / ``Seats`` for scripted bots with their own arguments per ship and
 env block next to them, and ``mutate`` / ``tune_script``, ScriptBot's tuning walk,
 ``Recorder`` (record.py) whole games of chosen envs recorded on the device, as
-the reference's ``Game`` / ``Tick`` logs with the networks' Q values.
+the reference's ``Game`` / ``Tick`` logs with the networks' Q values, ``Fork``
+(fork.py) env state copied between slots on the device -- ``BatchedEnv.fork_from``,
+``snapshot`` and ``restore`` -- and ``Lookahead`` the one-ply search bot on it.
 """
 from .config import (Bodies, Config, DEFAULT_CONFIG, Game, SOLO_CONFIG,  # noqa: F401
                      SOLO_EASY_CONFIG, State, Tick, generate_configs)
@@ -26,3 +28,5 @@ from .league import (Pool, Script, Seats, compare, find_better, mutate, p_better
                      tune_script)
 from . import record  # noqa: F401
 from .record import Recorder  # noqa: F401
+from . import fork  # noqa: F401
+from .fork import Fork, Lookahead  # noqa: F401

@@ -11,6 +11,7 @@
     qpool   libastro_qpool.so    astro_qpool.h
     trace   libastro_trace.so    astro_trace.h
     seats   libastro_seats.so    astro_seats.h
+    fork    libastro_fork.so     astro_fork.h
 
 The libraries are built in-tree by ``__graft_entry__.build()`` (hipcc
 --offload-arch=gfx950).  There is no fallback: if a library is missing or its
@@ -418,6 +419,17 @@ _SEATS_SYMBOLS = {
 }
 
 
+FORK_GAME, FORK_STREAM = 1, 2    # include/astro_fork.h ASTRO_FORK_GAME / ASTRO_FORK_STREAM
+
+# libastro_fork.so: env state copied between slots on the device, a library of its own (include/astro_fork.h)
+_FORK_SYMBOLS = {
+    'astro_fork_abi_version': (ctypes.c_int, []),
+    'astro_fork_last_error': (ctypes.c_char_p, []),
+    'astro_fork': (ctypes.c_int, [ctypes.POINTER(AstroParams), ctypes.POINTER(AstroState), ctypes.POINTER(AstroState),
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+}
+
+
 class AstroError(RuntimeError):
     pass
 
@@ -445,6 +457,7 @@ LIBS = collections.OrderedDict((r.key, r) for r in (
     _row('qpool', 'libastro_qpool.so', 'astro_qpool.hip', 'ASTRO_QPOOL_LIB', 1, 'astro_qpool_', _QPOOL_SYMBOLS),
     _row('trace', 'libastro_trace.so', 'astro_trace.hip', 'ASTRO_TRACE_LIB', 1, 'astro_trace_', _TRACE_SYMBOLS),
     _row('seats', 'libastro_seats.so', 'astro_seats.hip', 'ASTRO_SEATS_LIB', 1, 'astro_seats_', _SEATS_SYMBOLS),
+    _row('fork', 'libastro_fork.so', 'astro_fork.hip', 'ASTRO_FORK_LIB', 1, 'astro_fork_', _FORK_SYMBOLS),
 ))
 LIB_PATH, ABI_VERSION = LIBS['hip'].path, LIBS['hip'].abi
 QNET_LIB_PATH, QNET_ABI_VERSION = LIBS['qnet'].path, LIBS['qnet'].abi
@@ -456,10 +469,11 @@ QDUEL_LIB_PATH, QDUEL_ABI_VERSION = LIBS['qduel'].path, LIBS['qduel'].abi
 QPOOL_LIB_PATH, QPOOL_ABI_VERSION = LIBS['qpool'].path, LIBS['qpool'].abi
 TRACE_LIB_PATH, TRACE_ABI_VERSION = LIBS['trace'].path, LIBS['trace'].abi
 SEATS_LIB_PATH, SEATS_ABI_VERSION = LIBS['seats'].path, LIBS['seats'].abi
+FORK_LIB_PATH, FORK_ABI_VERSION = LIBS['fork'].path, LIBS['fork'].abi
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
 _lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = None
-_qopt_lib = _qduel_lib = _qpool_lib = _trace_lib = _seats_lib = None
+_qopt_lib = _qduel_lib = _qpool_lib = _trace_lib = _seats_lib = _fork_lib = None
 
 
 def _load(key, path):
@@ -520,6 +534,7 @@ load_qduel, check_qduel = _public('qduel')
 load_qpool, check_qpool = _public('qpool')
 load_trace, check_trace = _public('trace')
 load_seats, check_seats = _public('seats')
+load_fork, check_fork = _public('fork')
 
 
 def stream_ptr(device):

@@ -808,6 +808,41 @@ class BatchedEnv:
         self.check_errors()
         return dict(zip(_lib.STAT_NAMES, v))
 
+    # ------------------------------------------------------------------ forks
+
+    def fork_from(self, src, src_ids=None, dst_ids=None, game=True, stream=True):
+        """Env ``dst_ids[j]`` of this batch becomes env ``src_ids[j]`` of
+        ``src`` (a ``BatchedEnv`` of this shape, possibly this one; ids None:
+        the identity), on the device in one launch (astro_fork,
+        include/astro_fork.h): ``game`` the current game, ``stream`` the future
+        games -- with both, the copy steps bit for bit like its source from
+        then on; with ``game`` alone it keeps its own seed stream and pending
+        game, as ``load_host`` does.  Builds and applies a ``fork.Fork`` (keep
+        one yourself to copy the same pairs again without the host checks).
+        ``info()`` raises until the next step."""
+        from .fork import Fork
+        Fork(src, self, src_ids, dst_ids, game, stream).apply()
+
+    def snapshot(self):
+        """An opaque holder of every env's state now (game and stream), for
+        ``restore``: the seven state arrays and nothing else, filled by an
+        identity fork."""
+        from .fork import Fork, Snapshot
+        snap = Snapshot(self)
+        Fork(self, snap).apply()
+        return snap
+
+    def restore(self, snap):
+        """Put a ``snapshot()`` of this env (or of one of its shape) back:
+        the batch then steps as it did from the snapshot on, through every
+        auto-reset."""
+        from .fork import Fork, Snapshot
+        if type(snap) is not Snapshot:
+            raise ValueError('restore takes what snapshot() returned')
+        if snap.n_env != self.n_env:
+            raise ValueError('the snapshot holds %d envs, this env %d' % (snap.n_env, self.n_env))
+        Fork(snap, self).apply()
+
     # ----------------------------------------------------- host import/export
 
     def to_host(self):
