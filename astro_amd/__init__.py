@@ -14,7 +14,9 @@ env block next to them, and ``mutate`` / ``tune_script``, ScriptBot's tuning wal
 ``Recorder`` (record.py) whole games of chosen envs recorded on the device, as
 the reference's ``Game`` / ``Tick`` logs with the networks' Q values, ``Fork``
 (fork.py) env state copied between slots on the device -- ``BatchedEnv.fork_from``,
-``snapshot`` and ``restore`` -- and ``Lookahead`` the one-ply search bot on it.
+``snapshot`` and ``restore`` -- and ``Lookahead`` the one-ply search bot on it,
+``search`` (search.py) that search's value reduction in one launch, and
+``Distiller`` (train.py) a Q-network trained on the search's values.
 """
 from .config import (Bodies, Config, DEFAULT_CONFIG, Game, SOLO_CONFIG,  # noqa: F401
                      SOLO_EASY_CONFIG, State, Tick, generate_configs)
@@ -22,7 +24,7 @@ from .env import BatchedEnv, Observation  # noqa: F401
 from .replay import ReplayBuffer  # noqa: F401
 from .actor import EpsilonGreedy, Episodes  # noqa: F401
 from .optim import SGD, Adagrad, Adam, RMSprop  # noqa: F401
-from .train import QTrainer  # noqa: F401
+from .train import Distiller, QTrainer  # noqa: F401
 from . import league  # noqa: F401
 from .league import (Pool, Script, Seats, compare, find_better, mutate, p_better, tournament,  # noqa: F401
                      tune_script)
@@ -30,3 +32,4 @@ from . import record  # noqa: F401
 from .record import Recorder  # noqa: F401
 from . import fork  # noqa: F401
 from .fork import Fork, Lookahead  # noqa: F401
+from . import search  # noqa: F401

@@ -17,6 +17,12 @@ The libraries are built in-tree by ``__graft_entry__.build()`` (hipcc
 --offload-arch=gfx950).  There is no fallback: if a library is missing or its
 ABI version differs, every entry point of it raises.  tests/test_libraries.py
 checks every row against its header and its built library.
+
+``LIBS`` is this module's own table: every row's struct mirrors and symbol
+table live here.  A module that carries its binding itself registers its row
+in ``MORE`` with ``register`` (astro_amd/search.py: libastro_search.so,
+astro_search.h); ``row(key)`` finds a row of either, ``rows()`` lists both, and
+``build()`` compiles both.
 """
 import collections
 import ctypes
@@ -471,6 +477,29 @@ TRACE_LIB_PATH, TRACE_ABI_VERSION = LIBS['trace'].path, LIBS['trace'].abi
 SEATS_LIB_PATH, SEATS_ABI_VERSION = LIBS['seats'].path, LIBS['seats'].abi
 FORK_LIB_PATH, FORK_ABI_VERSION = LIBS['fork'].path, LIBS['fork'].abi
 
+# rows registered by the modules that hold their own binding (see the module docstring)
+MORE = collections.OrderedDict()
+
+
+def row(key):
+    """The row of ``LIBS`` or ``MORE`` with this key."""
+    return LIBS[key] if key in LIBS else MORE[key]
+
+
+def rows():
+    """Every row, ``LIBS``' first."""
+    return list(LIBS.values()) + list(MORE.values())
+
+
+def register(key, file, source, env, abi, prefix, symbols):
+    """Add a row to ``MORE`` (once per key) and return its public (load, check) pair."""
+    if key in LIBS or key in MORE:
+        raise ValueError('the library key %r is taken' % key)
+    MORE[key] = _row(key, file, source, env, abi, prefix, symbols)
+    globals()[MORE[key].handle] = None
+    return _public(key)
+
+
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)
 _lib = _qnet_lib = _qtrain_lib = _replay_lib = _actor_lib = None
 _qopt_lib = _qduel_lib = _qpool_lib = _trace_lib = _seats_lib = _fork_lib = None
@@ -479,7 +508,7 @@ _qopt_lib = _qduel_lib = _qpool_lib = _trace_lib = _seats_lib = _fork_lib = None
 def _load(key, path):
     """The library of LIBS[key], loaded from `path` and typed on the first call.  Raises if
     it is absent or stale."""
-    L = LIBS[key]
+    L = row(key)
     lib = globals()[L.handle]
     if lib is not None:
         return lib
@@ -506,15 +535,15 @@ def _load(key, path):
 
 def _check(key, rc, what):
     """Raise the library's last error for the entry point `what` that returned rc != 0."""
-    msg = getattr(_load(key, LIBS[key].path), LIBS[key].error)().decode(errors='replace')
+    msg = getattr(_load(key, row(key).path), row(key).error)().decode(errors='replace')
     raise AstroError('%s failed (%d): %s' % (what, rc, msg))
 
 
 def _public(key):
     """The library's public pair; what a call per step pays is one lookup and one compare."""
-    loaded, handle = globals(), LIBS[key].handle
+    loaded, handle = globals(), row(key).handle
 
-    def load(path=LIBS[key].path):
+    def load(path=row(key).path):
         lib = loaded[handle]
         return lib if lib is not None else _load(key, path)
 

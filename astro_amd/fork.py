@@ -8,7 +8,9 @@ include/astro_fork.h), and what is built on the copy:
                ``BatchedEnv.snapshot()`` returns and ``restore()`` takes
 ``Lookahead``  a one-ply search bot: each of the six controls is tried in a
                copy of the game, a scripted bot plays the copy on for a
-               horizon, and the control whose copy ends best is played
+               horizon, and the control whose copy ends best is played;
+               optionally a Q-network values the copies that do not end, and
+               the other ship's six replies are tried too
 
 A fork copies the current game (``game``), the future games (``stream``: the
 pending seed, the generate_configs cursor and its MT19937 ring) or both; with
@@ -24,7 +26,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, search
 
 MT_N = 624
 
@@ -169,69 +171,129 @@ class Lookahead:
     ``values()``: fork everything, one ``step`` in which ``ship`` plays
     control a in branch a and the other ship ``base``'s control on the copy,
     then ``rollout(horizon - 1, base)`` for every ship in one launch
-    (auto-reset on).  A branch's value is ``discount ** t * reward[t, ship]``
-    at its FIRST done tick t < horizon, 0 if it does not end.
+    (auto-reset on), then one launch of the value reduction
+    (``search.reduce``, include/astro_search.h).  A branch's value is
+    ``discount ** t * reward[t, ship]`` at its FIRST done tick t < horizon, 0
+    if it does not end.
     ``controls()``: ``base``'s own control for ``ship`` unless some control's
     value is strictly greater than that one's, then the first maximal one --
     so a horizon in which nothing ends plays exactly ``base``.
 
     base: a policy that depends on the state alone ('script', 'nothing'; under
     'random' the copies draw other controls than ``env`` would, see the module
-    docstring).  script_args: ScriptBot's, for ``base``."""
+    docstring).  script_args: ScriptBot's, for ``base``.
+
+    leaf (keyword): a ``qnet.QNetwork`` for ``env.S`` ships with six outputs
+    (ValueError otherwise).  A branch that does not end is then worth
+    ``discount ** horizon * max_a Q(s_K, a)``, the network's view of ``ship``
+    in the branch's last state (``scratch.qvalues`` in the per-ship form, one
+    more launch, into ``leaf_q``, a buffer kept here), instead of 0.  ``leaf``
+    is a plain attribute: a trainer may swap or refresh it between calls.
+
+    reply (keyword; a two-ship env): the other ship's first control is
+    searched too.  The scratch env has ``36 * n_env`` envs -- six times the
+    state memory and six times the step and rollout work of the default, e.g.
+    36,864 scratch envs for 1,024 -- with the plan env i -> 36 i .. 36 i + 35;
+    in branch (a, o) = 36 i + 6 a + o ``ship`` plays a and the other ship o at
+    the first step, ``base`` plays both from then on, and a control's value is
+    its minimum over o."""
 
     NCONTROL = 6
 
-    def __init__(self, env, ship=0, horizon=32, base='script', discount=0.995, script_args=None):
+    def __init__(self, env, ship=0, horizon=32, base='script', discount=0.995, script_args=None, *, leaf=None,
+                 reply=False):
         from .env import BatchedEnv
         if not 0 <= int(ship) < env.S:
             raise ValueError('ship must be in [0, %d), got %s' % (env.S, ship))
         if int(horizon) < 1:
             raise ValueError('horizon must be >= 1, got %s' % horizon)
+        if reply and env.S != 2:
+            raise ValueError('reply needs a two-ship env')
+        if leaf is not None:
+            from .qnet import QNetwork
+            if not isinstance(leaf, QNetwork) or leaf.nships != env.S or leaf.nout != self.NCONTROL:
+                raise ValueError('leaf must be a QNetwork for %d ships with %d outputs' % (env.S, self.NCONTROL))
         self.env, self.ship, self.horizon, self.base = env, int(ship), int(horizon), base
         self.discount, self.script_args = float(discount), script_args
+        self.leaf, self.reply = leaf, bool(reply)
         A, N = self.NCONTROL, env.n_env
+        R = self.replies = A if self.reply else 1
         kernel = [k for k, v in _lib.KERNELS.items() if v == env.params.kernel][0]
-        self.scratch = BatchedEnv(env.config, N * A, device=env.device, b_cap=env.b_cap, p_pad=env.p_pad,
+        self.scratch = BatchedEnv(env.config, N * A * R, device=env.device, b_cap=env.b_cap, p_pad=env.p_pad,
                                   dtype=env.dtype, env_offset=env.env_offset, auto_reset=True, kernel=kernel,
                                   use_key_table=env.key_table is not None, planets_only=env.planets_only,
                                   mem=env.mem)
-        self.plan = Fork(env, self.scratch, np.repeat(np.arange(N), A), np.arange(N * A))
-        self._branch = (torch.arange(N * A, device=env.device) % A).to(torch.int8)
-        self._gamma = torch.from_numpy((self.discount ** np.arange(self.horizon)).astype(np.float32)).to(env.device)
+        self.plan = Fork(env, self.scratch, np.repeat(np.arange(N), A * R), np.arange(N * A * R))
+        m = torch.arange(N * A * R, device=env.device)
+        self._branch = (m // R % A).to(torch.int8)
+        self._reply = (m % R).to(torch.int8) if self.reply else None
+        self._gamma = torch.from_numpy(search.gammas(self.discount, self.horizon)).to(env.device)
+        self.leaf_q = None
 
-    def values(self):
-        """float32 [N, 6]: the value of each control for ``ship`` now."""
-        sc, A = self.scratch, self.NCONTROL
+    def _search(self, own):
+        """The branched step and rollout, reduced: ``search.reduce``'s result."""
+        sc = self.scratch
         self.plan.apply()
         c = sc.controls(self.base, script_args=self.script_args)
         c[:, self.ship] = self._branch
+        if self.reply:
+            c[:, 1 - self.ship] = self._reply
+        self._first_control = c
         _, r0, d0 = sc.step(c, auto_reset=True)
-        reward, done = r0[None, :, self.ship], d0[None]
+        r = d = None
         if self.horizon > 1:
             r, d = sc.rollout(self.horizon - 1, self.base, auto_reset=True, script_args=self.script_args)
-            reward, done = torch.cat([reward, r[:, :, self.ship]]), torch.cat([done, d])
-        ended = done != 0                                          # [K, 6 N]
-        first = ended.to(torch.int8).argmax(0, keepdim=True)       # the first done tick (0 where none)
-        value = torch.where(ended.any(0), self._gamma[first[0]] * reward.gather(0, first)[0],
-                            torch.zeros((), dtype=torch.float32, device=sc.device))
-        return value.view(self.env.n_env, A)
+        q = None
+        if self.leaf is not None:
+            if self.leaf_q is None:
+                self.leaf_q = torch.zeros((sc.n_env, sc.S, self.NCONTROL), dtype=torch.float32, device=sc.device)
+            nets = [None] * sc.S
+            nets[self.ship] = self.leaf
+            q = sc.qvalues(nets, out=self.leaf_q)
+        self._outputs = (r0, d0, r, d, q)      # (alive until the launch has run; what the tests reduce again)
+        return search.reduce(r0, d0, r, d, gamma=self._gamma, ship=self.ship, replies=self.replies, leaf=q, own=own)
 
-    def controls(self):
-        """int8 [N]: the control ``ship`` plays now (deterministic)."""
-        v = self.values()
-        own = self.env.controls(self.base, script_args=self.script_args)[:, self.ship].to(torch.int64)
+    def _own(self):
+        return self.env.controls(self.base, script_args=self.script_args)[:, self.ship].contiguous()
+
+    def values(self):
+        """float32 [N, 6]: the value of each control for ``ship`` now."""
+        return self._search(None)
+
+    def controls(self, values=None):
+        """int8 [N]: the control ``ship`` plays now (deterministic).  values:
+        the tensor ``values()`` just returned for this state -- the decision is
+        then taken on it (a few torch ops) instead of searching again."""
+        if values is None:
+            return self._search(self._own())[1]
+        v = values
+        own = self._own().to(torch.int64)
         best, arg = v.max(1).values, v.argmax(1)    # argmax: the first maximal control
         return torch.where(best > v.gather(1, own[:, None])[:, 0], arg, own).to(torch.int8)
 
-    def play(self, opponent='script', games=1, max_ticks=None):
+    def play(self, opponent='script', games=1, max_ticks=None, record=None):
         """``env.play``'s (winner int64 [N, games], length int64 [N, games]):
         every env plays its next ``games`` games from its current state, each
         tick ``controls()`` for ``ship`` and ``env.controls(opponent)`` for the
         other ship (a two-ship env), pushed to an ``actor.Episodes`` as
         ``play_q`` does; the device count of finished games is read every 64
-        ticks only."""
+        ticks only.  record: a ``record.Recorder`` of ``env`` made with ``q=6``
+        and at least 64 slots -- every tick is recorded with the search's six
+        values as ``ship``'s Q values (``bot_data``; the other ship has none),
+        and the ring is drained every 64 ticks, where the loop synchronises
+        anyway; the games end up in ``record.games``."""
         from . import actor
         env, G = self.env, int(games)
+        q_out = played = None
+        if record is not None:
+            if getattr(record, 'env', None) is not env:
+                raise ValueError('record must be a Recorder of this env')
+            if record.ticks < 64:
+                raise ValueError('play drains the recorder every 64 ticks: it needs ticks >= 64, got %d' % record.ticks)
+            if not record.wants_q or record.nout != self.NCONTROL:
+                raise ValueError('record must be made with q=%d: the search has %d values' % ((self.NCONTROL,) * 2))
+            q_out = torch.zeros((env.n_env, env.S, self.NCONTROL), dtype=torch.float32, device=env.device)
+            played = [s == self.ship for s in range(env.S)]
         ep = actor.Episodes(env, G)
         limit = max_ticks if max_ticks is not None else G * (env.schedule.timeout_tick + 1) + 64
         t = 0
@@ -241,10 +303,18 @@ class Lookahead:
             for _ in range(64):
                 c = env.controls(opponent, tick0=t) if env.S > 1 else \
                     torch.empty((env.n_env, 1), dtype=torch.int8, device=env.device)
-                c[:, self.ship] = self.controls()
+                v, mine = self._search(self._own())
+                c[:, self.ship] = mine
+                if record is not None:
+                    q_out[:, self.ship] = v
+                    record.state(c, q_out, played)
                 _, r, d = env.step(c, auto_reset=True)
+                if record is not None:
+                    record.result(r, d)
                 ep.push(r, d)
                 t += 1
+            if record is not None:
+                record.drain()
             if int(ep.got.min()) >= G:
                 break
         return ep.winner.to(torch.int64), ep.ticks.to(torch.int64)

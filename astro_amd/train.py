@@ -13,6 +13,10 @@ Options, all off by default: an ``astro_amd.optim`` update rule instead of
 ``sgd_step``, a frozen target network for the targets, Double-DQN targets
 (astro_qopt.h), and an opponent as ship 1: a scripted bot, a fixed network or a
 snapshot of the learner refreshed every K steps (astro_qduel.h).
+
+``Distiller`` is the other way to train the same network: no replay and no
+bootstrap, the targets are a ``fork.Lookahead``'s search values for all six
+controls of every state (astro_search.h).
 """
 import torch
 
@@ -180,4 +184,104 @@ class QTrainer:
         ``record.Recorder`` of ``eval_env`` (see ``play_q``): the games of its
         envs, with the network's Q values, as rl.train saves its validation
         game (rl.py:354-355).  Synchronises."""
+        return eval_env._play_q(self.net, opponent, games, None, None, 0, record).summary()
+
+
+class Distiller:
+    """Train a Q-network on a search's values: ``teacher`` (a
+    ``fork.Lookahead`` of ``env`` for ship 0) plays ship 0 and, on every tick,
+    its ``values()`` -- one number for EACH of the six controls of every env --
+    are the regression targets of all six outputs of ``net``.  Nothing
+    bootstraps: a target is the search's own estimate.
+
+    One ``tick()``: ``f = env.features()``; ``v = teacher.values()``; ship 0
+    plays ``teacher.controls(values=v)`` (then ``explore.apply``, an
+    ``actor.EpsilonGreedy`` of ``env``, if given); the other ship plays
+    ``env.controls(opponent)`` ('script', 'nothing' or 'random'; its control is
+    final); ``env.step``; then ONE training step through ``net.step`` (with an
+    ``astro_amd.optim`` optimizer) or ``net.sgd_step(lr=lr)`` on 6 n samples --
+    every chosen env's features six times, with the actions 0..5 and the
+    targets ``v``'s row.  Six targets per state are six samples to the existing
+    gradient kernel.  envs_per_step: n, the envs trained on per tick (default
+    all): tick t takes the n entries from position ``t * n`` (cyclically) of a
+    permutation of the envs that is drawn once from ``seed``.
+
+    leaf_sync=J > 0: expert iteration -- ``teacher.leaf`` is kept a
+    ``net.clone()`` (set here, replacing what the teacher had), hard-copied
+    from ``net`` after every J-th step; the teacher then values unended
+    branches with the student.  J = 0 leaves the teacher as it is."""
+
+    def __init__(self, env, net, teacher, optimizer=None, lr=1e-2, opponent='script', explore=None, envs_per_step=None,
+                 leaf_sync=0, seed=0):
+        from .fork import Lookahead
+        from .qnet import QNetwork
+        if not isinstance(teacher, Lookahead) or teacher.env is not env:
+            raise ValueError('teacher must be a fork.Lookahead of this env')
+        if teacher.ship != 0:
+            raise ValueError('teacher must play ship 0, not ship %d' % teacher.ship)
+        if not isinstance(net, QNetwork) or net.nships != env.S or net.nout != Lookahead.NCONTROL:
+            raise ValueError('net must be a QNetwork for %d ships with %d outputs' % (env.S, Lookahead.NCONTROL))
+        if env.S > 1 and opponent not in ('script', 'nothing', 'random'):
+            raise ValueError("opponent must be 'script', 'nothing' or 'random', got %r" % (opponent,))
+        if explore is not None and getattr(explore, 'env', None) is not env:
+            raise ValueError('explore belongs to another env')
+        n = env.n_env if envs_per_step is None else envs_per_step
+        if not (isinstance(n, int) and not isinstance(n, bool) and 1 <= n <= env.n_env):
+            raise ValueError('envs_per_step must be an int in [1, %d], got %r' % (env.n_env, envs_per_step))
+        if not (isinstance(leaf_sync, int) and not isinstance(leaf_sync, bool) and leaf_sync >= 0):
+            raise ValueError('leaf_sync must be an int >= 0 (steps between hard copies; 0: off), got %r' % (leaf_sync,))
+        self.env, self.net, self.teacher, self.optimizer = env, net, teacher, optimizer
+        self.lr, self.opponent, self.explore, self.seed = float(lr), opponent, explore, int(seed)
+        self.envs_per_step, self.leaf_sync = n, leaf_sync
+        self.nstep = 0          # ticks, which are optimisation steps, so far
+        self.last = None
+        A = Lookahead.NCONTROL
+        self._action = (torch.arange(n * A, device=env.device) % A).to(torch.int8)
+        self._order = None
+        if n < env.n_env:
+            g = torch.Generator().manual_seed(self.seed)
+            self._order = torch.randperm(env.n_env, generator=g).to(env.device)
+            self._window = torch.arange(n, device=env.device)
+        if leaf_sync:
+            teacher.leaf = net.clone()
+
+    def tick(self):
+        """One tick of acting and one training step.  Returns the mean loss as
+        a device scalar; no host synchronisation."""
+        env, net, teacher, t = self.env, self.net, self.teacher, self.nstep
+        f = env.features()
+        v = teacher.values()
+        c = torch.empty((env.n_env, env.S), dtype=torch.int8, device=env.device)
+        c[:, 0] = teacher.controls(values=v)
+        if self.explore is not None:
+            self.explore.apply(c, t)
+        if env.S > 1:       # (after the exploration: the other ship's control is final)
+            c[:, 1] = env.controls(self.opponent, self.seed, t)[:, 1]
+        env.step(c)
+        if self._order is not None:
+            ids = self._order[(self._window + t * self.envs_per_step) % env.n_env]
+            f, v = f[ids], v[ids]
+        f6 = f.repeat_interleave(v.shape[1], 0)
+        target = v.reshape(-1)
+        if self.optimizer is None:
+            loss = net.sgd_step(f6, self._action, target, lr=self.lr)
+        else:
+            loss = net.step(f6, self._action, target, self.optimizer)
+        self.nstep += 1
+        if self.leaf_sync and self.nstep % self.leaf_sync == 0:
+            teacher.leaf.copy_from(net)
+        self.last = loss.mean()
+        return self.last
+
+    def run(self, ticks):
+        """``ticks`` calls of ``tick``; returns the last mean loss (or None)."""
+        out = None
+        for _ in range(int(ticks)):
+            out = self.tick()
+        return out
+
+    def validate(self, eval_env, games=1, opponent=None, record=None):
+        """``QTrainer.validate``'s: the NETWORK plays greedily, without search
+        -- ``eval_env.play_q(net, opponent, games)`` as
+        ``actor.Episodes.summary()``.  Synchronises."""
         return eval_env._play_q(self.net, opponent, games, None, None, 0, record).summary()
