@@ -15,8 +15,11 @@ env block next to them, and ``mutate`` / ``tune_script``, ScriptBot's tuning wal
 the reference's ``Game`` / ``Tick`` logs with the networks' Q values, ``Fork``
 (fork.py) env state copied between slots on the device -- ``BatchedEnv.fork_from``,
 ``snapshot`` and ``restore`` -- and ``Lookahead`` the one-ply search bot on it,
-``search`` (search.py) that search's value reduction in one launch, and
-``Distiller`` (train.py) a Q-network trained on the search's values.
+``search`` (search.py) that search's value reduction in one launch,
+``Distiller`` (train.py) a Q-network trained on the search's values, and ``es``
+(es.py) an antithetic evolution strategy on the packed weights -- ``Population``
+and ``ESTrainer``: perturb, play the members on blocks of envs, score, estimate
+the gradient, all on the device (csrc/astro_es.hip, include/astro_es.h).
 """
 from .config import (Bodies, Config, DEFAULT_CONFIG, Game, SOLO_CONFIG,  # noqa: F401
                      SOLO_EASY_CONFIG, State, Tick, generate_configs)
@@ -33,3 +36,5 @@ from .record import Recorder  # noqa: F401
 from . import fork  # noqa: F401
 from .fork import Fork, Lookahead  # noqa: F401
 from . import search  # noqa: F401
+from . import es  # noqa: F401
+from .es import ESTrainer, Population  # noqa: F401

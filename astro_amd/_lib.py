@@ -21,8 +21,11 @@ checks every row against its header and its built library.
 ``LIBS`` is this module's own table: every row's struct mirrors and symbol
 table live here.  A module that carries its binding itself registers its row
 in ``MORE`` with ``register`` (astro_amd/search.py: libastro_search.so,
-astro_search.h); ``row(key)`` finds a row of either, ``rows()`` lists both, and
-``build()`` compiles both.
+astro_search.h); ``row(key)`` finds a row of either and ``rows()`` lists both.
+``LATER`` is a third table of the same kind, filled by ``register_later``
+(astro_amd/es.py: libastro_es.so, astro_es.h): ``row(key)`` finds its rows too,
+``all_rows()`` is ``rows()`` plus them, and ``build()`` compiles ``all_rows()``.
+A key is taken once across the three tables.
 """
 import collections
 import ctypes
@@ -481,9 +484,16 @@ FORK_LIB_PATH, FORK_ABI_VERSION = LIBS['fork'].path, LIBS['fork'].abi
 MORE = collections.OrderedDict()
 
 
+# rows registered after ``rows()`` was fixed as LIBS + MORE: listed by ``all_rows()`` only
+LATER = collections.OrderedDict()
+
+
 def row(key):
-    """The row of ``LIBS`` or ``MORE`` with this key."""
-    return LIBS[key] if key in LIBS else MORE[key]
+    """The row of ``LIBS``, ``MORE`` or ``LATER`` with this key."""
+    for table in (LIBS, MORE):
+        if key in table:
+            return table[key]
+    return LATER[key]
 
 
 def rows():
@@ -491,13 +501,27 @@ def rows():
     return list(LIBS.values()) + list(MORE.values())
 
 
+def all_rows():
+    """Every row of the three tables: ``rows()``, then ``LATER``'s."""
+    return rows() + list(LATER.values())
+
+
+def _register(table, key, file, source, env, abi, prefix, symbols):
+    if key in LIBS or key in MORE or key in LATER:
+        raise ValueError('the library key %r is taken' % key)
+    table[key] = _row(key, file, source, env, abi, prefix, symbols)
+    globals()[table[key].handle] = None
+    return _public(key)
+
+
 def register(key, file, source, env, abi, prefix, symbols):
     """Add a row to ``MORE`` (once per key) and return its public (load, check) pair."""
-    if key in LIBS or key in MORE:
-        raise ValueError('the library key %r is taken' % key)
-    MORE[key] = _row(key, file, source, env, abi, prefix, symbols)
-    globals()[MORE[key].handle] = None
-    return _public(key)
+    return _register(MORE, key, file, source, env, abi, prefix, symbols)
+
+
+def register_later(key, file, source, env, abi, prefix, symbols):
+    """Add a row to ``LATER`` (once per key across the three tables) and return its public (load, check) pair."""
+    return _register(LATER, key, file, source, env, abi, prefix, symbols)
 
 
 # the loaded libraries (tools/ab.py sets _lib back to None to load another build)

@@ -405,6 +405,23 @@ class QNetwork:
         other._workspace = None
         return other
 
+    @classmethod
+    def view(cls, row, nships, nout):
+        """A QNetwork whose ``weights`` IS ``row`` (a contiguous float32
+        [nparams] device tensor, e.g. a row of a population's member matrix):
+        made like ``clone()`` without the copy, so whatever writes the row
+        changes what this network plays."""
+        n = sum(int(np.prod(s)) for _, s in shapes(nships, nout))
+        if (not torch.is_tensor(row) or tuple(row.shape) != (n,) or row.dtype != torch.float32
+                or row.device.type != 'cuda' or not row.is_contiguous()):
+            raise ValueError('row must be a contiguous float32 [%d] tensor on a HIP device' % n)
+        other = cls.__new__(cls)
+        other.nships, other.nout, other.device = int(nships), int(nout), row.device
+        other.weights = row
+        other.c = _lib.AstroQNet(weights=row.data_ptr(), nships=other.nships, nout=other.nout)
+        other._workspace = None
+        return other
+
     def copy_from(self, other):
         """Copy another QNetwork's weights in, on the device (no host trip)."""
         if (other.nships, other.nout) != (self.nships, self.nout):
